@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark: BASELINE.json's metric, "Mrays/sec + Msamples/sec ... Cornell 1024spp and Bistro 256spp".
 
-Default run (the driver's `python bench.py --gpus N --steps K --warmup W`):
+Plain run (the driver's `python bench.py --gpus N --steps K --warmup W`): the headline only.
   * C1 = BASELINE configs[1]: lumo's Cornell box, PathTrace, 1024x1024 @ 1024 spp.  One "step" is
     the whole frame: every (256-spp batch, 16x16 tile) RenderTask (renderer.rs:179-204),
     4 batches x 4096 tiles = 1.07e9 camera paths.  W warmup frames, then K timed frames.  These
-    are the top-level fields of the JSON line.
+    are the top-level fields of the JSON line (with the roofline of the timed frames, which costs
+    no run of its own).
+  * `--dump-outputs DIR` writes what the last timed frame returned to its caller as DIR/<name>.npy
+    (float64): see dump_outputs().  Same arguments, same inputs: two builds compare file by file.
+With `--full` the run goes on to everything else it measures, as further fields of the same line:
+  * the CPU baseline of each workload (`--cpu-baseline`, see below);
   * C3 = BASELINE configs[3]: the Bistro stand-in, PathTrace, 1920x1080 @ 256 spp, one timed
     frame after a 1-spp warmup frame (`--bistro-frames`, 0 disables).  Reported under "c3" with
     its own ms_per_step, roofline and CPU baseline.
@@ -42,6 +47,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
 SEED = 0x5EED_1234
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: all files together stay below this
 # Algorithmic bytes per unit: f64 data touched by the algorithm.
 B_AABB, B_KD, B_TRI = 48, 16, 84           # slab test bounds; kd split node; 3 vertices + indices
 B_CLOSEST_IO = 48 + 20  # ray in + hit out
@@ -66,7 +72,7 @@ UNIT_STAGES = {"k_bounce_q+k_bounce_tail": [1, 4], "k_closest": [1], "k_shadow":
 
 
 def progress(msg):
-    """A progress line on stderr (long default runs: the C4 share and the CPU baselines)."""
+    """A progress line on stderr (long --full runs: the C4 share and the CPU baselines)."""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
@@ -82,6 +88,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also measure the rest: the CPU baselines (--cpu-baseline) and, "
+                         "with --config c1, the C3 / C2 / C4-share frames (--bistro-frames, --dragon-frames, "
+                         "--c4-share)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline run returned as DIR/<name>.npy (float64)")
     ap.add_argument("--config", default="c1", choices=["c1", "c2", "c3", "c4"],
                     help="c1 Cornell 1024^2@1024 (BASELINE configs[1]); c2 dragon.rs 1920x1080@256 with the "
                          "871k-triangle stand-in (configs[2]); c3 Bistro stand-in 1920x1080@256 (configs[3]); "
@@ -89,16 +101,19 @@ def main():
     ap.add_argument("--res", type=int, default=None, help="square resolution override")
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--bistro-frames", type=int, default=1,
-                    help="with --config c1: also time this many C3 Bistro frames at 1920x1080@256 (0: skip)")
+                    help="with --full and --config c1: also time this many C3 Bistro frames at 1920x1080@256 "
+                         "(0: skip)")
     ap.add_argument("--bistro-spp", type=int, default=256)
     ap.add_argument("--dragon-frames", type=int, default=1,
-                    help="with --config c1: also time this many C2 dragon frames at 1920x1080@256 (0: skip)")
+                    help="with --full and --config c1: also time this many C2 dragon frames at 1920x1080@256 "
+                         "(0: skip)")
     ap.add_argument("--c4-share", default="0/8",
-                    help="with --config c1: also time this rank share R/N of the C4 caustics BDPT frame "
+                    help="with --full and --config c1: also time this rank share R/N of the C4 caustics BDPT frame "
                          "(1024^2@4096) on this GPU (empty: skip)")
     ap.add_argument("--max-paths", type=int, default=1 << 23, help="paths in flight per wavefront")
     ap.add_argument("--max-vertices", type=int, default=0, help="BDPT vertex storage per subpath (0 = 128)")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the oracle on the host (rank 0, N=1)")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="with --full: time the oracle on the host (rank 0, N=1)")
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="target CPU work per baseline run (x3 repeats)")
     ap.add_argument("--share", default=None,
                     help="R/N: render only rank R's share of an N-rank run (tile %% N == R) in this single "
@@ -129,14 +144,15 @@ def main():
         pg = dist
 
     main_res = run(args.config, args, ws, rank, local, pg, steps=args.steps, warmup=args.warmup,
-                   res=args.res, spp=args.spp, share=args.share)
+                   res=args.res, spp=args.spp, share=args.share, dump_dir=args.dump_outputs)
     extra = {}
-    if args.config == "c1" and args.bistro_frames > 0:
+    further = args.full and args.config == "c1"  # a plain run stops at the headline
+    if further and args.bistro_frames > 0:
         extra["c3"] = run("c3", args, ws, rank, local, pg, steps=args.bistro_frames, warmup=1, spp=args.bistro_spp,
                           warm_spp=1)
-    if args.config == "c1" and args.dragon_frames > 0:
+    if further and args.dragon_frames > 0:
         extra["c2"] = run("c2", args, ws, rank, local, pg, steps=args.dragon_frames, warmup=1, warm_spp=1)
-    if args.config == "c1" and args.c4_share and ws == 1:
+    if further and args.c4_share and ws == 1:
         # one rank's load of the 8-GPU C4 run (BASELINE configs[4] is quoted on 8 GPUs), on this GPU
         extra["c4_share"] = run("c4", args, ws, rank, local, pg, steps=1, warmup=1, warm_spp=1, share=args.c4_share)
     if rank == 0:
@@ -152,10 +168,12 @@ def main():
         pg.destroy_process_group()
 
 
-def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, warm_spp=None, share=None):
+def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, warm_spp=None, share=None,
+        dump_dir=None):
     """Render `steps` timed frames of `config` (after `warmup` frames, at `warm_spp` if given) and
     return the JSON record (rank 0 fields complete).  `share` "R/N": only the tiles with
-    tile % N == R (one rank's load of an N-rank run), in this process."""
+    tile % N == R (one rank's load of an N-rank run), in this process.  `dump_dir`: write the
+    last timed frame's outputs there (dump_outputs)."""
     import lumo_amd as L
     from lumo_amd import _ffi
     from lumo_amd.dist import TileQueue, shard_tasks, tasks_of_tiles, tiles_per_batch
@@ -185,6 +203,8 @@ def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, wa
     accel = dev.scene_info().accel  # 0 when the build refused the scene
     lib = _ffi.load()
 
+    last = []  # with dump_dir: (tasks, buffers, results) of each render call of the latest frame
+
     def step(arr):
         if bdpt:
             splat_film[:] = 0.0
@@ -192,6 +212,8 @@ def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, wa
                                           splat_film=splat_film, max_vertices=args.max_vertices)
         else:
             bufs, res_ = dev.render_tasks(arr, max_paths=args.max_paths)
+        if dump_dir:  # references only: what this call returned stays alive until the next frame
+            last.append((arr, bufs, res_))
         return sum(r.num_queries for r in res_), sum(r.num_camera_rays for r in res_), sum(r.num_rays for r in res_)
 
     def barrier():
@@ -202,6 +224,7 @@ def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, wa
             pg.barrier()
 
     for _ in range(warmup):
+        del last[:]
         step(warm_arr)
     progress(f"{config}: warmup done, timing {steps} step(s)")
     dev.set_option("timing", 1)
@@ -211,6 +234,7 @@ def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, wa
     q = cams = rays = 0
     dynamic = getattr(args, "schedule", "static") == "dynamic" and ws > 1 and not share
     for _ in range(steps):
+        del last[:]  # the previous frame's outputs are freed before this one's are allocated
         if dynamic:
             # every rank builds one queue per timed frame, in the same order (TileQueue keys)
             for tl in TileQueue(W, H, ws, chunk=args.chunk):
@@ -223,6 +247,9 @@ def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, wa
     barrier()  # lumo_render_tiles returns only after its stream has drained
     elapsed = time.perf_counter() - t0
     progress(f"{config}: {elapsed / steps * 1e3:.1f} ms per step")
+    if dump_dir:
+        dump_outputs(dump_dir, last, splat_film, rank, ws)
+        del last[:]
     dev.set_option("timing", 0)
     st = dev.stats()
     # busy time (union of launch intervals) of every stage and of the roofline units
@@ -249,7 +276,7 @@ def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, wa
         wkey = f"{config}_share" if share and pmc_traffic(f"{config}_share", "source") else config
         roof = roofline(st, n_shadow_rays(scene), bdpt=bdpt, workload=wkey, elapsed=elapsed, busy=busy, accel=accel)
         cpu = cpu_baseline(scene, cam, tasks, tiles, args, W, H, spp, wl, repeats=wl.get("cpu_repeats", CPU_REPEATS)) \
-            if (args.cpu_baseline and ws == 1) else None
+            if (args.full and args.cpu_baseline and ws == 1) else None
         out = {
             "metric": "Mrays/s",
             # traversed queries only: the shadow records answered without a traversal (their BSDF
@@ -300,6 +327,47 @@ def run(config, args, ws, rank, local, pg, steps, warmup, res=None, spp=None, wa
             out["share"] = share  # one rank's load of an N-rank run, timed on this one GPU
     del scene
     return out
+
+
+def dump_outputs(out_dir, calls, splat_film, rank, ws):
+    """--dump-outputs: what the render calls of the last timed frame returned, as float64 .npy
+    files of at most DUMP_BYTES in all (`calls`: (tasks, buffers, results) per call, in order).
+      counters.npy    [tasks, 3]  num_camera_rays, num_rays, num_queries of every task's result
+      rgb_w.npy       the {sum w rgb, sum w} tile buffers (4 f64 per pixel, row-major) of the
+                      tasks listed in rgb_w_tasks.npy, concatenated in that order: every task if
+                      they fit, else a sample drawn with a fixed seed (the same tasks every run)
+      rgb_w_tasks.npy indices of those tasks within the frame's render calls, ascending
+      splat_film.npy  BDPT only: the light-tracing splat film [H, W, 3], or, if that is over half
+                      the budget, the pixels listed in splat_film_pixels.npy, [pixels, 3]
+    With several ranks each writes its own share, the names ending in _rank<r>."""
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if ws > 1 else ""
+    rng = np.random.default_rng(SEED)
+    budget = DUMP_BYTES
+
+    def save(name, a):
+        nonlocal budget
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        budget -= a.nbytes + 128  # the .npy header
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), a)
+
+    bufs = [b for _, bs, _ in calls for b in bs]
+    save("counters", np.array([(r.num_camera_rays, r.num_rays, r.num_queries) for _, _, rs in calls for r in rs],
+                              dtype=np.float64).reshape(len(bufs), 3))
+    if splat_film is not None:
+        px = splat_film.reshape(-1, 3)
+        if px.nbytes > DUMP_BYTES // 2:
+            pick = np.sort(rng.choice(len(px), DUMP_BYTES // 2 // 32, replace=False))
+            save("splat_film_pixels", pick)
+            save("splat_film", px[pick])
+        else:
+            save("splat_film", splat_film)
+    order = rng.permutation(len(bufs))
+    cost = np.cumsum([bufs[i].nbytes + 8 for i in order])  # a buffer and its entry in rgb_w_tasks
+    pick = np.sort(order[:int(np.searchsorted(cost, budget - 256, side="right"))])
+    save("rgb_w_tasks", pick)
+    save("rgb_w", np.concatenate([bufs[i] for i in pick]) if len(pick) else np.zeros(0))
+    progress(f"outputs of the last timed step: {len(pick)} of {len(bufs)} tile buffers in {out_dir}")
 
 
 def build_config(name, res=None, spp_override=None):

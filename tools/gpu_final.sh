@@ -1,5 +1,5 @@
 #!/bin/bash
-# Check of the tree on the GPU box (repo root): full GPU suite, smoke, default bench line, then
+# Check of the tree on a GPU machine (repo root): full GPU suite, smoke, the bench --full line, then
 # (optional, "trace") a rocprofv3 kernel trace of one C1 frame.  Every GPU step has its own time
 # limit and the chain stops at the first failure.  Usage: tools/gpu_final.sh <tag> [trace]
 set -eo pipefail
@@ -10,7 +10,7 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -v --timeout 300 --timeout-m
   || { tail -30 $OUT/pytest_gpu.log; exit 1; }
 tail -1 $OUT/pytest_gpu.log
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1
-timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 head -c 600 $OUT/bench.json; echo
 if [ "${2:-}" = "trace" ]; then
   REPO=$(pwd)

@@ -488,7 +488,7 @@ lumo_status lumo_scene_info(void* ctx, lumo_scene_info_t* info);
  * the access width of the path kernels. */
 lumo_status lumo_debug_stream(void* ctx, size_t n);
 /* Diagnostics (ABI 10): the device's exclusive prefix sum (device/scan.h, the BDPT item lists' scan)
- * of n host uint32 counts into out. */
+ * of n host uint32 counts into out (n = 0: nothing is written). */
 lumo_status lumo_debug_scan(void* ctx, const uint32_t* in, uint32_t* out, size_t n);
 
 #ifdef __cplusplus

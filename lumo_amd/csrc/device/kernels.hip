@@ -3774,7 +3774,8 @@ lumo_status lumo_debug_stream(void* ctx, size_t n) {
 // Diagnostics: the device exclusive scan (scan.h) of n host uint32 counts into out (host).
 lumo_status lumo_debug_scan(void* ctx, const uint32_t* in, uint32_t* out, size_t n) {
     Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c || !in || !out || n == 0 || n > 0xffffffffu) return LUMO_ERR_INVALID;
+    if (!c || !in || !out || n > 0xffffffffu) return LUMO_ERR_INVALID;
+    if (n == 0) return LUMO_OK;  // nothing to scan: out is left untouched
     HIPCHK(hipSetDevice(c->device));
     uint32_t* buf = nullptr;
     const size_t nb = (size_t)scan_blocks((uint32_t)n);

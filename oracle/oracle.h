@@ -53,7 +53,10 @@ void oracle_set_tone_map(int kind, double arg);
 /* Integrator for subsequent renders: LUMO_INTEGRATOR_PATH_TRACE or LUMO_INTEGRATOR_BDPT. */
 void oracle_set_integrator(int integrator);
 /* Acceleration structure of subsequent calls: 0 lumo's BVHs + kd-trees (default), 1 the wide BVH of
- * lumo_amd's LUMO_OPT_ACCEL = 1 (same structure as the upload builds, walk restated here). */
+ * lumo_amd's LUMO_OPT_ACCEL = 1 (same structure as the upload builds, walk restated here).
+ * Oracle only (the reference both walks are tested against, tests/test_brute.py): 2 brute force, every
+ * primitive of every object and light tested with the wide walk's acceptance tests and no structure
+ * (oracle_trace's closest and visibility queries); 3 the same in reversed primitive order. */
 void oracle_set_accel(int accel);
 /* Diagnostics: the wide BVH built for `scene`: info[8] = {ok, nodes, leaf triangle records, walk
  * stack need, node levels, objects root ref, lights root ref, 0}; non-null buffers (sized from a

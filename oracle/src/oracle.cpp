@@ -171,6 +171,7 @@ Color spec_sample(const lumo_spectrum& s, const Lambda& L) {
 struct Scene {
     const lumo_scene_desc* d;
     const wbvh::Accel* w = nullptr;  // wide accel mode (oracle_set_accel(1)): the walks run on it
+    int brute = 0;  // oracle_set_accel(2 / 3): no structure, every primitive tested (1 in order, 2 reversed)
     const double* dense(int idx) const { return d->dense_spectra + 95 * idx; }
     V3 vert(int i) const { return V3{d->vertices[3 * i], d->vertices[3 * i + 1], d->vertices[3 * i + 2]}; }
     int num_shadow_rays() const {  // scene.rs:90-92
@@ -183,7 +184,8 @@ struct Scene {
     }
 };
 // Accel mode of subsequent calls (oracle_set_accel): 0 lumo's structures, 1 the wide BVH, built by
-// wbvh_build.h and cached per scene content (a C3-size build takes seconds).
+// wbvh_build.h and cached per scene content (a C3-size build takes seconds); 2 / 3 brute force (no
+// structure is built or read; the reference the walks are checked against, never the product's).
 int g_accel = 0;
 std::mutex g_wide_mu;
 struct WideCache {
@@ -218,7 +220,8 @@ uint64_t desc_hash(const lumo_scene_desc* d) {
 }
 Scene make_scene(const lumo_scene_desc* d) {
     Scene sc{d};
-    if (g_accel) {
+    if (g_accel == 2 || g_accel == 3) sc.brute = g_accel - 1;
+    if (g_accel == 1) {
         const uint64_t h = desc_hash(d);
         std::lock_guard<std::mutex> lk(g_wide_mu);
         if (!g_wide.valid || g_wide.hash != h) {
@@ -731,11 +734,14 @@ double bvh_hit_t(const Scene& sc, const BvhView& b, const Ray& r, double t_min, 
 // scene.rs:119-147. kind: 0 miss, 1 object, 2 light.
 bool wide_scene_hit(const Scene& sc, const Ray& r, Hit* h, int* kind, int* which, int* prim, Counters& C);
 bool wide_occluded(const Scene& sc, const Ray& r, double t_max, Counters& C);
+bool brute_scene_hit(const Scene& sc, const Ray& r, Hit* h, int* kind, int* which, int* prim, Counters& C);
+bool brute_occluded(const Scene& sc, const Ray& r, double t_max, Counters& C);
 bool scene_hit(const Scene& sc, const Ray& r, Hit* h, int* kind, int* which, Counters& C, int* prim = nullptr) {
     C.closest++;
     int pr = -1;
-    if (sc.w) {
-        const bool f = wide_scene_hit(sc, r, h, kind, which, &pr, C);
+    if (sc.w || sc.brute) {
+        const bool f = sc.brute ? brute_scene_hit(sc, r, h, kind, which, &pr, C)
+                                : wide_scene_hit(sc, r, h, kind, which, &pr, C);
         if (prim) *prim = pr;
         return f;
     }
@@ -766,6 +772,11 @@ bool scene_hit_light(const Scene& sc, const Ray& r, int light, Hit* out, Counter
     Hit lh;
     if (!object_hit(sc, sc.d->lights[light], r, 0.0, INF, &lh, C)) return false;
     const double t_max = lh.t - EPSILON;
+    if (sc.brute) {
+        if (brute_occluded(sc, r, t_max, C)) return false;
+        *out = lh;
+        return true;
+    }
     if (sc.w) {
         if (wide_occluded(sc, r, t_max, C)) return false;
         *out = lh;
@@ -994,6 +1005,70 @@ bool wide_scene_hit(const Scene& sc, const Ray& r, Hit* h, int* kind, int* which
 bool wide_occluded(const Scene& sc, const Ray& r, double t_max, Counters& C) {  // scene.rs:171-189
     if (wide_walk(sc, sc.w->obj_root, sc.d->objects, sc.w->obj_blas, r, 0.0, t_max, true, C).t < t_max) return true;
     return wide_walk(sc, sc.w->light_root, sc.d->lights, sc.w->light_blas, r, 0.0, t_max, true, C).t < t_max;
+}
+
+// ------------------------------------------------------------------ brute force
+// The reference of the walks above: every primitive of every object, in the instance's space
+// (ray.rs:24-31, unnormalised), with the tests the wide walk accepts a hit by (triangle_hit GEO,
+// sphere_hit) against the running closest t; no box, no tree, no order but the tables' (reversed
+// when sc.brute == 2, which shows the rays whose answer depends on the visiting order).
+WRes brute_walk(const Scene& sc, const lumo_object* objs, int n_objs, const Ray& rw, double t_min, double t_max,
+                bool any, Counters& C) {
+    WRes h{t_max, -1, -1};
+    const bool rev = sc.brute == 2;
+    for (int a = 0; a < n_objs; ++a) {
+        const int oi = rev ? n_objs - 1 - a : a;
+        const lumo_object& ob = objs[oi];
+        const Ray rl = ob.xform >= 0 ? ray_to_local(xform_of(sc.d->transforms[ob.xform]), rw, false) : rw;
+        Hit g;
+        if (ob.type == LUMO_OBJ_SPHERE) {
+            if (sphere_hit(ob, rl, t_min, h.t, &g) && g.t < h.t) {
+                h = WRes{g.t, PRIM_SPHERE_O, oi};
+                if (any) return h;
+            }
+            continue;
+        }
+        const int n = ob.type == LUMO_OBJ_TRIANGLE ? 1 : ob.num_tris;
+        for (int b = 0; b < n; ++b) {
+            const int ti = ob.tri_base + (rev ? n - 1 - b : b);
+            const double t = triangle_hit(sc, ti, rl, t_min, h.t, true, &g, C);
+            if (t < h.t) {
+                h = WRes{t, ti, oi};
+                if (any) return h;
+            }
+        }
+    }
+    return h;
+}
+// Scene::hit (scene.rs:119-147) as wide_scene_hit: the objects, then the lights below the objects' t
+bool brute_scene_hit(const Scene& sc, const Ray& r, Hit* h, int* kind, int* which, int* prim, Counters& C) {
+    double t_max = INF;
+    bool found = false;
+    *kind = 0;
+    Hit tmp;
+    Counters rebuild;
+    const WRes o = brute_walk(sc, sc.d->objects, sc.d->num_objects, r, 0.0, INF, false, C);
+    if (o.obj >= 0 && object_hit_prim(sc, sc.d->objects[o.obj], o.tri, r, 0.0, t_max, &tmp, rebuild)) {
+        *h = tmp;
+        found = true;
+        *kind = 1;
+        *which = o.obj;
+        *prim = o.tri;
+        t_max = tmp.t;
+    }
+    const WRes l = brute_walk(sc, sc.d->lights, sc.d->num_lights, r, 0.0, t_max, false, C);
+    if (l.obj >= 0 && object_hit_prim(sc, sc.d->lights[l.obj], l.tri, r, 0.0, t_max, &tmp, rebuild)) {
+        *h = tmp;
+        found = true;
+        *kind = 2;
+        *which = l.obj;
+        *prim = l.tri;
+    }
+    return found;
+}
+bool brute_occluded(const Scene& sc, const Ray& r, double t_max, Counters& C) {  // scene.rs:171-189
+    if (brute_walk(sc, sc.d->objects, sc.d->num_objects, r, 0.0, t_max, true, C).t < t_max) return true;
+    return brute_walk(sc, sc.d->lights, sc.d->num_lights, r, 0.0, t_max, true, C).t < t_max;
 }
 
 // ------------------------------------------------------------------ materials

@@ -12,6 +12,8 @@ ORACLE_PATH = os.path.join(ROOT, "oracle", "_build", "liblumo_oracle.so")
 ORACLE_GLIBC_PATH = os.path.join(ROOT, "oracle", "_build", "liblumo_oracle_glibc.so")
 
 WAVEFRONT, LUMO_ORDER = 0, 1
+# oracle_set_accel values (oracle_trace only for the brute modes)
+LUMO, WIDE, BRUTE, BRUTE_REV = 0, 1, 2, 3
 
 
 class Counters(C.Structure):
@@ -151,7 +153,9 @@ def trace_paths(scene_desc, camera_desc, task, path=None, integrator=0, sampler=
 
 def trace(scene_desc, origins, dirs, lights=None, accel=0, with_prim=False):
     """Scene::hit (lights None) or Scene::hit_light per ray: (t, kind, object, counters), with the
-    triangle (wide accel only; -1 otherwise) before the counters when with_prim."""
+    triangle (wide accel and brute force; -1 otherwise) before the counters when with_prim.
+    accel: 0 lumo's structures, 1 the wide BVH, BRUTE (2) every primitive tested with no structure
+    at all, BRUTE_REV (3) the same in reversed primitive order (oracle only, oracle/oracle.h)."""
     lib = load()
     n = len(origins)
     o = np.ascontiguousarray(origins, dtype=np.float64)

@@ -106,3 +106,136 @@ def textured_obj_zip(path):
             z.writestr(n, b)
     path.write_bytes(bio.getvalue())
     return path
+
+
+# ---- builder edge scenes (tests/test_wide.py NAMES, tests/test_brute.py): each a few hundred
+# triangles at most, each aimed at one branch of the wide builder (wbvh_build.h)
+def _grey():
+    return L.Material.lambertian(L.Spectrum.from_rgb(0.5, 0.5, 0.5))
+
+
+def _lamp(s, y=3.0, half=0.25):
+    """Two triangle lights (a quad) above the origin, facing down."""
+    v = np.array([(-half, y, -half), (half, y, -half), (half, y, half), (-half, y, half)], dtype=float)
+    s.add_mesh(v, [(0, 1, 2, 3)], L.Material.light(NS("WHITE")), light=True)
+
+
+def concentric_triangles():
+    """Coplanar triangles (plane y = 0) whose boxes share one centre: 20 around the origin and 16
+    around (3, 0, 0), with dyadic sizes so the box centres coincide exactly.  No SAH bin separates
+    centres that coincide, so after the split between the two groups the builder halves the lists
+    (count / 2): 20 -> 10 -> leaves of 5, 16 -> leaves of 8 = LEAF_MAX."""
+    v, f = [], []
+    for cx, n in ((0.0, 20), (3.0, 16)):
+        for k in range(n):
+            h = 0.25 + 0.125 * k
+            f.append(tuple(range(len(v), len(v) + 3)))
+            v += [(cx - h, 0.0, -h), (cx + h, 0.0, -h), (cx, 0.0, h)]
+    s = L.Scene()
+    s.add_mesh(np.array(v), f, _grey())
+    _lamp(s)
+    return s
+
+
+def degenerate_mesh():
+    """A small knot with every fifth triangle duplicated, plus zero-area triangles: two corners
+    equal, three corners equal, three corners collinear."""
+    from lumo_amd.procedural import torus_knot_tube
+    v, q = torus_knot_tube(16, 4)
+    q = np.asarray(q)
+    f = [t for a, b, c, d in q for t in ((a, b, c), (a, c, d))]
+    f += f[::5]
+    n = len(v)
+    v = np.concatenate([v, [(0.0, 0.0, 0.0), (0.5, 0.25, -0.5), (1.0, 0.5, -1.0)]])
+    f += [(0, 0, 1), (2, 2, 2), (n, n + 1, n + 2), (n, n + 2, n + 1), (5, 9, 5)]
+    s = L.Scene()
+    s.add_mesh(v, f, _grey())
+    _lamp(s)
+    return s
+
+
+def flat_mesh(n=9):
+    """An n x n grid of quads in the plane y = 0.25 (exact in f32, so outward rounding keeps the
+    boxes flat) with irregular spacing: every box of the objects' tree has zero height."""
+    rng = np.random.default_rng(3)
+    x = np.cumsum(rng.uniform(0.05, 0.4, n + 1)) - 1.0
+    z = np.cumsum(rng.uniform(0.05, 0.4, n + 1)) - 1.0
+    v = np.array([(xi, 0.25, zi) for xi in x for zi in z])
+    f = [(i * (n + 1) + j, i * (n + 1) + j + 1, (i + 1) * (n + 1) + j + 1, (i + 1) * (n + 1) + j)
+         for i in range(n) for j in range(n)]
+    s = L.Scene()
+    s.add_mesh(v, f, _grey())
+    _lamp(s)
+    return s
+
+
+ZOO_SHIFT = (1e4 + 0.1, -1e4 - 0.3, 1e4 + 0.7)
+
+
+def translated_zoo(shift=ZOO_SHIFT):
+    """The material zoo's triangles re-added as plain meshes at shifted coordinates: the vertices
+    are no f32 values and the outward rounding of the f32 boxes (~1e-3 at 1e4) is as large as the
+    gaps between the cubes and the floor."""
+    from rays import world_triangles
+    d = material_zoo().build().desc()
+    tri, light = world_triangles(d)
+    tri = tri + np.asarray(shift)
+    s = L.Scene()
+    for sel, is_light in ((light < 0, False), (light >= 0, True)):
+        t = tri[sel]
+        v = t.reshape(-1, 3)
+        f = np.arange(len(v)).reshape(-1, 3)
+        if not len(t):  # the zoo's light is a rectangle: keep a lamp under the roof instead
+            continue
+        s.add_mesh(v, [tuple(r) for r in f], L.Material.light(NS("WHITE")) if is_light else _grey(), light=is_light)
+    if not (light >= 0).any():
+        h, y = 0.2, 0.75
+        v = np.array([(-h, y, -1 - h), (h, y, -1 - h), (h, y, -1 + h), (-h, y, -1 + h)]) + np.asarray(shift)
+        s.add_mesh(v, [(0, 1, 2, 3)], L.Material.light(NS("WHITE")), light=True)
+    return s
+
+
+def scaled_instances():
+    """One mesh instanced twice: scale (1e-3, 1, 1e3), a rotation and a translation of 1e4 (the
+    instance's world box is padded by 1e-9 of its magnitude, wbvh_build.h xf_box), and scale 1."""
+    from lumo_amd.procedural import torus_knot_tube
+    v, f = torus_knot_tube(40, 5)
+    s = L.Scene()
+    s.add_mesh(v, f, _grey()).scale(1e-3, 1.0, 1e3).rotate_y(0.7).rotate_x(-0.2).translate(1e4, 0.5, -1e4)
+    s.add_mesh(v, f, _grey()).scale_uniform(1.0).rotate_z(0.3).translate(1e4 + 2.0, 0.0, -1e4 + 1.0)
+    v = np.array([(-1.0, 5.0, -1.0), (1.0, 5.0, -1.0), (1.0, 5.0, 1.0), (-1.0, 5.0, 1.0)]) + (1e4, 0.0, -1e4)
+    s.add_mesh(v, [(0, 1, 2, 3)], L.Material.light(NS("WHITE")), light=True)
+    return s
+
+
+def sphere_field(n=40):
+    """Spheres only (n objects, one sphere light): both trees hold object leaves and nothing else."""
+    rng = np.random.default_rng(11)
+    s = L.Scene()
+    for c, r in zip(rng.uniform(-2.0, 2.0, (n, 3)), rng.uniform(0.1, 0.6, n)):
+        s.add_sphere(float(r), _grey()).translate(*c)
+    s.add_sphere(0.4, L.Material.light(NS("WHITE")), light=True).translate(0.0, 3.5, 0.0)
+    return s
+
+
+def stadium():
+    """A teapot in a stadium: a 2-triangle floor of size 1e4 and a 200-triangle knot of size 1 on it.
+    The floor falls by 1e-4 per unit of x, so its box is not flat: lumo's kd walk clips hits at a flat
+    leaf's exit (test_wide.py), which on an axis-aligned floor of this size loses 8 % of the generic
+    rays and would say nothing about the wide builder."""
+    from lumo_amd.procedural import torus_knot_tube
+    v, f = torus_knot_tube(25, 4)
+    v = (v - v.min(0)) / (v.max(0) - v.min(0)).max()
+    s = L.Scene()
+    h, dy = 5e3, 0.5
+    s.add_mesh(np.array([(-h, dy, -h), (h, -dy, -h), (h, -dy, h), (-h, dy, h)]), [(0, 3, 2, 1)], _grey())
+    s.add_mesh(v + (0.3, 0.0, -0.2), f, _grey())
+    _lamp(s, y=4.0)
+    return s
+
+
+EDGE_SCENES = {"concentric": (concentric_triangles, (0.3, 2.0, 1.0)), "degenerate": (degenerate_mesh, (0.0, 0.5, 4.0)),
+               "flat": (flat_mesh, (0.2, 2.0, 0.5)),
+               "zoo_translated": (translated_zoo, ZOO_SHIFT),
+               "scaled_instances": (scaled_instances, (1e4 + 1.0, 1.0, -1e4 + 6.0)),
+               "sphere_field": (sphere_field, (0.0, 0.3, 6.0)), "stadium": (stadium, (3.0, 1.5, 2.0))}

@@ -46,17 +46,26 @@ def c3():
 
 
 def _arrays(desc):
+    if desc.num_vertices == 0:  # a scene of spheres only
+        return np.zeros((0, 3)), np.zeros(0, dtype=np.dtype(_ffi.Triangle))
     v = np.ctypeslib.as_array(desc.vertices, shape=(desc.num_vertices, 3))
     tris = np.ctypeslib.as_array(desc.triangles, shape=(desc.num_triangles,))
     return v, tris
+
+
+def _bounds(desc):
+    """Bounds of the scene's vertices; of the objects' BVH root for a scene without any."""
+    v, _ = _arrays(desc)
+    if len(v):
+        return v.min(0), v.max(0)
+    return np.array(desc.object_nodes[0].bmin[:]), np.array(desc.object_nodes[0].bmax[:])
 
 
 def _closest_rays(desc, eye, n, seed):
     """Half camera-like rays from the bench eye, half rays from random points of the scene's
     bounds in random directions (the secondary-ray mix)."""
     rng = np.random.default_rng(seed)
-    v, _ = _arrays(desc)
-    lo, hi = v.min(0), v.max(0)
+    lo, hi = _bounds(desc)
     m = n // 2
     o1 = np.repeat(np.asarray(eye, dtype=np.float64)[None], m, 0)
     d1 = (rng.uniform(lo, hi, size=(m, 3)) - o1)
@@ -73,7 +82,7 @@ def _visibility_rays(desc, n, seed):
     rng = np.random.default_rng(seed)
     v, tris = _arrays(desc)
     lights = np.ctypeslib.as_array(desc.lights, shape=(desc.num_lights,))
-    lo, hi = v.min(0), v.max(0)
+    lo, hi = _bounds(desc)
     o = rng.uniform(lo, hi, size=(n, 3))
     li = rng.integers(0, desc.num_lights, size=n).astype(np.int32)
     d = rng.normal(size=(n, 3))  # the environment sphere: any direction

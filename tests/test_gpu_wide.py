@@ -215,22 +215,27 @@ def test_wide_ray_sort_matches_oracle(mode):
     _tiles_cmp(bufs, res, obufs, ores)
 
 
-@pytest.mark.parametrize("n", [1, 2047, 2048, 2049, 5_000_001])
+@pytest.mark.parametrize("n", [0, 1, 2047, 2048, 2049, 524288, 524289, 526336, 526337, 5_000_001])
 def test_device_exclusive_scan(n):
     """The hand-written exclusive scan (scan.h, two launches) that replaced the library scan of the
-    BDPT item lists and splat taps, at sizes around its 2 048-count tile and across ~2 400 tiles."""
+    BDPT item lists and splat taps, at sizes around its 2 048-count tile, around 256 tiles
+    (524 288) and 257 tiles (526 336: the block-prefix loop of k_scan_apply, 256 totals per pass,
+    runs a second pass from block 257 on) and across ~2 400 tiles.  Nothing is written past the n
+    counts; n = 0 leaves `out` untouched."""
     import ctypes as C
     rng = np.random.default_rng(n)
-    a = rng.integers(0, 40, size=n).astype(np.uint32)
-    out = np.zeros(n, dtype=np.uint32)
+    a = rng.integers(0, 40, size=n + 1).astype(np.uint32)
+    guard = np.uint32(0xDEADBEEF)
+    out = np.full(n + 1, guard, dtype=np.uint32)
     d = L.Device(0)
     try:
         _ffi.check(_ffi.load().lumo_debug_scan(d.ctx, a.ctypes.data_as(_ffi.c_uint32_p),
                                                 out.ctypes.data_as(_ffi.c_uint32_p), C.c_size_t(n)), "debug_scan")
     finally:
         d.close()
-    want = np.concatenate([[0], np.cumsum(a, dtype=np.uint64)[:-1]]).astype(np.uint32)
-    np.testing.assert_array_equal(out, want)
+    want = (np.cumsum(a[:n], dtype=np.uint64) - a[:n]).astype(np.uint32)
+    np.testing.assert_array_equal(out[:n], want)
+    assert out[n] == guard
 
 
 def test_wide_lights_only_scene(dev):

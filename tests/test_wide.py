@@ -20,8 +20,8 @@ import lumo_amd as L
 import oracle_ffi as O
 from lumo_amd import scenes
 from lumo_amd.procedural import torus_knot_tube
-from scenes import material_zoo
-from test_gpu_scale import _closest_rays, _visibility_rays
+from scenes import EDGE_SCENES, material_zoo
+from test_gpu_scale import _arrays, _closest_rays, _visibility_rays
 from test_instances_lights import light_scene, sphere_scene
 
 NONE = -(1 << 31)
@@ -29,6 +29,9 @@ KDMESH, RECT, TRI, SPHERE = 0, 1, 2, 3
 
 
 def _scene(name):
+    if name in EDGE_SCENES:  # the builder's edge cases (tests/scenes.py)
+        make, eye = EDGE_SCENES[name]
+        return make(), eye
     if name == "cornell":
         return L.Scene.cornell_box(), (278.0, 273.0, -800.0)
     if name == "caustics":
@@ -53,7 +56,7 @@ def _scene(name):
 
 
 NAMES = ["cornell", "caustics", "zoo", "small_dragon", "tri_lights", "instanced_rect", "spheres", "bistro_small",
-         "lights_only"]
+         "lights_only"] + list(EDGE_SCENES)
 
 
 def _leaves(acc, root):
@@ -130,8 +133,7 @@ def test_wide_structure(name):
                     want[t] = i
         assert got == want, f"space {space}: leaves do not hold exactly the untransformed triangles"
         # records hold the scene's vertices
-        vtx = np.ctypeslib.as_array(d.vertices, shape=(d.num_vertices, 3))
-        tris = np.ctypeslib.as_array(d.triangles, shape=(d.num_triangles,))
+        vtx, tris = _arrays(d)
         for node, k, r in leaves[:50]:
             x = ~r
             for j in range((x >> 4), (x >> 4) + (x & 15)):

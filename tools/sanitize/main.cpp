@@ -10,6 +10,7 @@
 // Any ASan / UBSan finding aborts the process (halt_on_error), which the test treats as failure.
 #include <zlib.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -259,10 +260,53 @@ void tasks() {
     }
 }
 
+// oracle_trace on Cornell in the wide and the two brute-force modes (oracle_set_accel 1 / 2 / 3):
+// axis-parallel rays with both signs of zero and rays aimed at a corner of the scene; the modes
+// agree on t.
+void brute() {
+    void* b = lumo_builder_cornell_box();
+    void* s = lumo_builder_build(b);
+    CHECK(s);
+    lumo_scene_desc d;
+    CHECK(lumo_scene_get_desc(s, &d) == 0);
+    const size_t n = 600;
+    std::vector<double> o(3 * n), dir(3 * n), t[3];
+    std::vector<int32_t> kind(n), obj(n), prim(n), light(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a) o[3 * i + a] = 1.0 + (double)(rnd() % 5400) / 10.0;
+        if (i % 2) {
+            for (int a = 0; a < 3; ++a) dir[3 * i + a] = (rnd() & 1) ? 0.0 : -0.0;
+            dir[3 * i + rnd() % 3] = (rnd() & 1) ? 1.0 : -1.0;
+        } else {
+            double len = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                dir[3 * i + a] = d.vertices[a] - o[3 * i + a];
+                len += dir[3 * i + a] * dir[3 * i + a];
+            }
+            for (int a = 0; a < 3; ++a) dir[3 * i + a] /= std::sqrt(len);
+        }
+    }
+    const lumo_ray_soa rays{o.data(), dir.data(), nullptr, light.data()};
+    for (int any = 0; any < 2; ++any) {
+        for (int m = 0; m < 3; ++m) {
+            t[m].assign(n, 0.0);
+            lumo_hit_soa hits{t[m].data(), kind.data(), obj.data(), prim.data()};
+            oracle_counters c{};
+            oracle_set_accel(m + 1);
+            CHECK(oracle_trace(&d, &rays, n, &hits, any, &c) == 0);
+        }
+        oracle_set_accel(0);
+        for (size_t i = 0; i < n; ++i) CHECK(t[0][i] == t[1][i] && t[1][i] == t[2][i]);
+    }
+    lumo_scene_free(s);
+    lumo_builder_free(b);
+}
+
 }  // namespace
 
 int main() {
     cornell();
+    brute();
     textured();
     hostile();
     tasks();

@@ -15,12 +15,16 @@ HIPFLAGS := -O3 -std=c++17 -fPIC $(FPFLAGS) --offload-arch=$(ARCH) -Wall -Wno-un
 HOST_SRC := $(wildcard lumo_amd/csrc/host/*.cpp)
 BUILD    ?= build
 HOST_OBJ := $(patsubst lumo_amd/csrc/host/%.cpp,build/host/%.o,$(HOST_SRC))
-# kernels.hip: host orchestration, C ABI and the non-traversal kernels.  The traversal kernels
-# are instantiated once per kd stack class (launch.h STACK_CLASSES) in their own translation
-# units, so they compile in parallel: inst_pt.hip / inst_bd.hip built with -DLUMO_STK=<class>.
+# kernels.hip: the non-traversal kernels, the schedulers and the entry points that launch them;
+# ctx.hip (context, options) and upload.hip (scene, camera) are host code only and share ctx.h with
+# it.  The traversal kernels are instantiated once per kd stack class (launch.h STACK_CLASSES) in
+# their own translation units, so they compile in parallel: inst_pt.hip / inst_bd.hip built with
+# -DLUMO_STK=<class>.
 STK_CLASSES := 0 4 8 16 24 32 48 64
-DEV_OBJ  := $(BUILD)/device/kernels.o $(foreach k,$(STK_CLASSES),$(BUILD)/device/inst_pt_$(k).o $(BUILD)/device/inst_bd_$(k).o)
-DEV_H    := $(wildcard lumo_amd/csrc/device/*.h)
+MAIN_OBJ := $(BUILD)/device/kernels.o $(BUILD)/device/ctx.o $(BUILD)/device/upload.o
+DEV_OBJ  := $(MAIN_OBJ) $(foreach k,$(STK_CLASSES),$(BUILD)/device/inst_pt_$(k).o $(BUILD)/device/inst_bd_$(k).o)
+CTX_H    := lumo_amd/csrc/device/ctx.h lumo_amd/csrc/host/wbvh.h
+DEV_H    := $(filter-out $(CTX_H),$(wildcard lumo_amd/csrc/device/*.h))
 COMMON_H := $(wildcard lumo_amd/csrc/common/*.h) include/lumo_amd.h include/lumo_host.h
 
 LIB      ?= lumo_amd/liblumo_amd.so
@@ -33,7 +37,7 @@ build/host/%.o: lumo_amd/csrc/host/%.cpp $(COMMON_H) $(wildcard lumo_amd/csrc/ho
 	@mkdir -p build/host
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-$(BUILD)/device/kernels.o: lumo_amd/csrc/device/kernels.hip $(COMMON_H) $(DEV_H)
+$(MAIN_OBJ): $(BUILD)/device/%.o: lumo_amd/csrc/device/%.hip $(COMMON_H) $(DEV_H) $(CTX_H)
 	@mkdir -p $(BUILD)/device
 	$(HIPCC) $(HIPFLAGS) $(DEVFLAGS) -c $< -o $@
 

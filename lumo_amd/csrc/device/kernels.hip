@@ -1,4 +1,6 @@
-// MI355X wavefront path tracer: HIP kernels for gfx950 + host orchestration + C ABI.
+// MI355X wavefront path tracer: HIP kernels for gfx950, the schedulers that launch them and the
+// entry points of the C ABI that render, trace or time.  (The context and its options: ctx.hip;
+// the scene upload and the camera: upload.hip; what the three share: ctx.h.)
 //
 // One path slot per (tile task, pixel).  Per sample pass:
 //   k_camera   MultiJittered sample + camera ray + hero wavelengths  (integrator.rs:45-70)
@@ -22,20 +24,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <strings.h>
-#include <unistd.h>  // environ
 #include <deque>
-#include <new>
 #include <type_traits>
 #include <vector>
 
 #include "../../../include/lumo_amd.h"
 
 #define LUMO_MAIN_TU
-#include "../host/wbvh.h"
 #include "launch.h"
 #include "scan.h"
 #include "pt.h"
+#include "ctx.h"
 
 using namespace lumo;
 using namespace lumo::dev;
@@ -791,182 +790,10 @@ __global__ __launch_bounds__(BLOCK) void k_calib_write8(double* __restrict__ out
 }
 
 // ================================================================== host side
-#define HIPCHK(x)                                \
-    do {                                         \
-        hipError_t e__ = (x);                    \
-        if (e__ != hipSuccess) {                 \
-            last_hip_error() = e__;              \
-            return LUMO_ERR_HIP;                 \
-        }                                        \
-    } while (0)
-
-hipError_t& last_hip_error() {
-    static thread_local hipError_t e = hipSuccess;
-    return e;
-}
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-// Per-launch HIP event pairs, resolved at the synchronisation points the host loop already
-// has (queue-count readbacks), so timing adds no extra stalls.
-struct Timing {
-    std::vector<hipEvent_t> free_ev;
-    struct Pending {
-        int stage;
-        hipEvent_t a, b;
-    };
-    std::vector<Pending> pending;
-    hipEvent_t get() {
-        if (free_ev.empty()) {
-            hipEvent_t e;
-            (void)hipEventCreate(&e);
-            return e;
-        }
-        hipEvent_t e = free_ev.back();
-        free_ev.pop_back();
-        return e;
-    }
-    ~Timing() {
-        for (hipEvent_t e : free_ev) (void)hipEventDestroy(e);
-        for (const Pending& p : pending) {
-            (void)hipEventDestroy(p.a);
-            (void)hipEventDestroy(p.b);
-        }
-    }
-};
 
 // Merged passes of the fused pipeline (render_pipelined): at most MAX_MERGE (state.h) passes per
 // unit, by default as many as bring a unit to about kMergeTarget paths (a full 1024^2 frame: 1).
 constexpr uint64_t kMergeTarget = (uint64_t)1 << 21;
-
-// Execution options of a context (lumo_set_option; include/lumo_amd.h LUMO_OPT_*).  None of them
-// changes a result.  Defaults here, then the environment at lumo_create.
-struct Opts {
-    int timing = 0;
-    int lds = 1;                       // whole scene in LDS when it fits (48 KiB)
-    int top = 1;                       // TOP staging of larger scenes
-    int fused = -1;                    // n_shadow == 1: k_bounce_q instead of closest / shade / shadow (-1: when LDS-staged)
-    uint32_t tail_below = 1u << 16;    // n_shadow == 1: k_bounce_q tail mode below this many live paths
-                                       // (split passes; C2 4-spp frame 332 ms at 2^18, 312-319 ms at 2^16)
-    int pipeline = 3;                  // fused passes overlapped (render_pipelined): 0 off, else head streams (1-3)
-    int heads = 0;                     // pipelined passes: fused bounces per pass before the tail kernel (0: auto)
-    int merge = 0;                     // pipelined passes: passes merged into one head unit (0: auto)
-    int dyn = 0;                       // k_bounce_q: blocks fetch their paths from a counter (1) or take
-                                       // static grid-stride stripes (0; with lds_grid 384: C1 2 150 vs
-                                       // 2 350 ms per frame, 1/8 share 291 vs 367 ms, profiles/r05/ab/r05z*)
-    int bounce_threads = BLOCK;        // k_bounce_q (fused, not tail): threads per block (64, 128 or 256)
-    int split_pipe = 4;                // split schedule: units in flight (render_split_pipelined; 1 = sequential)
-    int split_groups = 2;              // split schedule: independent task groups
-    uint32_t bdpt_tail = 1u << 16;     // BDPT walks: k_bdpt_tail below this many live subpaths (0: never)
-    int bounce_ahead = 3;              // bounces enqueued ahead of the host's count snapshots
-    int lds_grid = 384;                // grid cap of the LDS-staged kernels: 1.5 blocks per CU (set from the
-                                       // CU count at creation); the three head streams' launches and the
-                                       // tail stream's share the CUs instead of queueing behind each other
-    int top_grid = 128;                // TOP kernels: blocks of 1 024 threads, one per CU on half the CUs (set from
-                                       // the CU count at creation), so the split pipeline's concurrent units
-                                       // share the GPU: C2 4-spp 305 -> 288 ms, C3 64-spp 4 084 -> 4 007 ms, its
-                                       // 1/8 share 723 -> 692 ms against one block on every CU (r05t*)
-    int top_kb = 160;                  // TOP set budget (KiB), at most the CU's LDS
-    int kd_lds = 8;                    // kd stack entries per thread in LDS in TOP kernels when room is left (C2 -3 %)
-    int stack_class = 0;               // kd stack class override (0: the scene's need)
-    int full_kernels = 0;              // general feature kernels for lean scenes too
-    int poison = 0;                    // new device buffers filled with 0xFF (reads before writes show as NaN / -1)
-    int tail_priority = 0;             // the pipelined passes' tail / film / ring stream at high priority
-    int top_kd = 1;                    // the TOP set's spare LDS holds the top treelets of the largest kd tree
-    int tail_bounces = -1;             // fused pipeline: fused bounces per pass on the tail stream before the tail kernel (-1 auto)
-    int bdpt_top = 1;                  // BDPT connection visibility of large scenes with TOP staging
-    int film_first = 0;                // fused pipeline, film on the tail stream: the film before the unit's last ring
-    int bdpt_groups = 2;               // BDPT: task groups rendered as concurrent pass chains (render_bdpt_groups)
-    int ray_sort = -1;                 // split bounces: closest-hit rays sorted (1 octant major, 2 origin major;
-                                       // -1 auto: 1 for deep kd trees, stack class >= 32: C2 4-spp frame
-                                       // 309 / 312 -> 302 ms; C3, class 24: 556 -> 563 ms, so off there)
-    int accel = 0;                     // upload: 0 lumo's BVHs + kd-trees, 1 the wide BVH (wbvh.h)
-};
-
-struct Ctx {
-    BounceArgs* bargs = nullptr;  // one k_bounce_q argument block per stream (stream, stream2, 3, 4)
-    int device = 0;
-    size_t lds_cu = 160 * 1024;     // LDS per CU (hipDeviceProp_t::maxSharedMemoryPerMultiProcessor)
-    size_t lds_block = 160 * 1024;  // LDS one block may allocate (sharedMemPerBlock)
-    Opts o;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;  // pipelined passes: each pass's tail, film and ring
-    hipStream_t stream3 = nullptr;  // pipelined passes (2-3 head streams): further head streams
-    hipStream_t stream4 = nullptr;
-    hipEvent_t pass_ev[4] = {}, tail_ev[4] = {}, cam_ev[4] = {}, film_ev[4] = {};
-    bool has_scene = false, has_camera = false;
-    DScene sc{};
-    DCam cam{};
-    std::vector<DevBuf> scene_bufs;
-    std::vector<DevBuf> work;  // grown on demand
-    lumo_stats stats{};
-    lumo_schedule_info sched{};  // of the last render
-    Timing tm;
-    int tone_map = LUMO_TONEMAP_NONE;  // of the lumo_render_tiles call in progress
-    double tone_arg = 0.0;
-    // per-bounce queue-count snapshots (pinned) and their completion events
-    static constexpr int SNAP_RING = 64;
-    uint32_t* snap = nullptr;
-    hipEvent_t snap_ev[SNAP_RING];
-    // integrator of the call in progress (BDPT: vertex storage per subpath, optional splat film)
-    int integrator = LUMO_INTEGRATOR_PATH_TRACE;
-    int max_vertices = 64;
-    double* splat_film = nullptr;
-    int debug_integrator = LUMO_INTEGRATOR_PATH_TRACE;  // lumo_debug_paths
-    int sampler = LUMO_SAMPLER_MULTI_JITTERED;          // of the lumo_render_tiles call in progress
-    int debug_sampler = LUMO_SAMPLER_MULTI_JITTERED;    // lumo_debug_paths
-    size_t split_sets_bytes = 0;  // work buffers already held by the extra pass sets (free-memory check)
-    // Launch intervals of the timed stages (ms from ref_ev, recorded before the first timed launch
-    // after a stats reset): their union is a stage's busy time, which does not count twice the
-    // time that launches on different streams overlap (lumo_stats_busy_ms)
-    hipEvent_t ref_ev = nullptr;
-    bool ref_recorded = false;
-    std::vector<std::pair<float, float>> intervals[LUMO_STAGE_COUNT];
-    // BDPT task groups (render_bdpt_groups): per-group work buffers, pinned item totals, events
-    std::vector<DevBuf> gwork;
-    uint32_t* bd_totals_h = nullptr;
-    hipEvent_t bd_ev[4] = {};
-    V3 sort_lo{0.0, 0.0, 0.0}, sort_scale{0.0, 0.0, 0.0};  // ray sorting: the scene's world box -> 512 cells per axis
-    int w_nodes = 0, w_tris = 0, w_stack = 0, w_depth = 0;     // the uploaded wide BVH (lumo_scene_info)
-};
-
-lumo_status dev_alloc(const Ctx& c, DevBuf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return LUMO_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    if (hipMalloc(&b.p, bytes) != hipSuccess) return LUMO_ERR_OOM;
-    b.bytes = bytes;
-    if (c.o.poison) {  // debug: new buffers all ones (NaN, -1)
-        // hipMemset runs on the null stream, which the context's non-blocking streams do not wait
-        // for: finish it here, or it could land after the render's own initialisation
-        (void)hipMemset(b.p, 0xFF, bytes);
-        (void)hipStreamSynchronize(nullptr);
-    }
-    return LUMO_OK;
-}
-
-template <typename T>
-lumo_status upload(Ctx& c, const T* host, size_t count, const T** dptr) {
-    c.scene_bufs.emplace_back();
-    DevBuf& b = c.scene_bufs.back();
-    const lumo_status st = dev_alloc(c, b, sizeof(T) * count);
-    if (st) return st;
-    if (count && host) HIPCHK(hipMemcpy(b.p, host, sizeof(T) * count, hipMemcpyHostToDevice));
-    *dptr = static_cast<const T*>(b.p);
-    return LUMO_OK;
-}
-
-void free_scene(Ctx& c) {
-    for (DevBuf& b : c.scene_bufs)
-        if (b.p) (void)hipFree(b.p);
-    c.scene_bufs.clear();
-    c.has_scene = false;
-}
 
 int ceil_div(uint64_t a, uint64_t b) { return (int)((a + b - 1) / b); }
 
@@ -977,20 +804,18 @@ enum WorkId {
     W_SH_OUT, W_SH_LIGHT, W_SH_FLAGS, W_G_SH, W_PDF_L, W_P_RGB, W_P_VALID, W_FILM, W_Q0, W_Q1,
     W_SQ, W_RQ, W_COUNTS, W_TCOUNT, W_TASKS, W_FIRST, W_RING_COST, W_RING_LUM, W_RING_PTR, W_DELTA, W_NUM_RAYS,
     W_TQUERIES, W_DUMP_RAD, W_DUMP_LAM, W_DUMP_RASTER, W_DUMP_DEPTH, W_DUMP_DELTA,
-    W_BD_LD, W_BD_LI, W_BD_CD, W_BD_CI, W_BD_SP, W_BD_SPN, W_BD_OVF, W_BD_CNT, W_BD_OFF, W_BD_RANGES, W_BD_TAPS,
-    W_BD_FILM, W_BD_SCAN, W_BD_REDO_LIST, W_BD_REDO_INDEX, W_BDR_LD, W_BDR_LI, W_BDR_CD, W_BDR_CI, W_BDR_SP,
-    W_BDR_SPN, W_BD_NL, W_BD_NC, W_BD_NITEMS, W_BD_IOFF, W_BD_DRAWS, W_BD_OK, W_BD_ITOTAL, W_BD_TERM, W_BD_PDF, W_BD_WDEPTH,
-    W_BD_CAMO, W_BD_CAMD, W_BD_RNG0, W_BD_LAM0, W_BDR_DRAWS, W_BDR_OK, W_BD_NB, W_BD_OFFB, W_BD_TERMB, W_BD_VIS, W_BD_AT, W_BD_AKIND, W_BD_AOBJ,
-    W_BD_ATRI, W_CHECKS, W_QS0_D, W_QS0_R, W_QS0_I, W_QS1_D, W_QS1_R, W_QS1_I, W_HQ_T, W_HQ_I, W_SQ_D, W_SQ_I,
+    W_BD_LD, W_BD_LI, W_BD_CD, W_BD_CI, W_BD_SP, W_BD_SPN, W_BD_OVF, W_BD_CNT, W_BD_OFF,
+    W_BD_FILM, W_BD_REDO_INDEX, W_BD_NL, W_BD_NC, W_BD_NITEMS, W_BD_IOFF, W_BD_DRAWS, W_BD_OK, W_BD_ITOTAL, W_BD_PDF,
+    W_BD_WDEPTH, W_BD_CAMO, W_BD_CAMD, W_BD_RNG0, W_BD_LAM0, W_BD_NB, W_BD_OFFB,
+    W_CHECKS, W_QS0_D, W_QS0_R, W_QS0_I, W_QS1_D, W_QS1_R, W_QS1_I, W_HQ_T, W_HQ_I, W_SQ_D, W_SQ_I,
     W_SQ_HD, W_SQ_HI, W_SQ_HR, W_RAD2, W_LAM2, W_RASTER2, W_DEPTH2, W_QUERIES2, W_P_VALID2, W_COUNTS2, W_QS2_D,
     W_QS2_R, W_QS2_I, W_QS3_D, W_QS3_R, W_QS3_I, W_RAD3, W_LAM3, W_RASTER3, W_DEPTH3, W_QUERIES3, W_P_VALID3,
     W_COUNTS3, W_QS4_D, W_QS4_R, W_QS4_I, W_QS5_D, W_QS5_R, W_QS5_I, W_RAD4, W_LAM4, W_RASTER4, W_DEPTH4,
     W_QUERIES4, W_P_VALID4, W_COUNTS4, W_QS6_D, W_QS6_R, W_QS6_I, W_QS7_D, W_QS7_R, W_QS7_I,
-    W_SQ_QL, W_BD_LM, W_BD_LMF, W_BD_CM, W_BD_CMF, W_BDR_LM, W_BDR_LMF, W_BDR_CM, W_BDR_CMF,
+    W_SQ_QL, W_BD_LM, W_BD_LMF, W_BD_CM, W_BD_CMF,
     W_SPLIT_SET1,  // render_split_pipelined sets 1..3: hits + NEE records, 8 buffers each
     W_SORT_SET0 = W_SPLIT_SET1 + 3 * 8,  // ray sorting of pass set k: keys, order, workspace
-    W_BD_ALIST = W_SORT_SET0 + 4 * 3,    // BDPT (a)-item trace lists
-    W_COUNT
+    W_COUNT = W_SORT_SET0 + 4 * 3
 };
 
 template <typename T>
@@ -1008,7 +833,7 @@ struct StageTimer {
     hipStream_t sm;
     hipEvent_t a{}, b{};
     StageTimer(Ctx& cc, bool enable, int st, hipStream_t stream = nullptr)
-        : c(cc), on(enable), stage(st), sm(stream ? stream : cc.stream) {
+        : c(cc), on(enable), stage(st), sm(stream ? stream : cc.streams[0]) {
         if (on) {
             a = c.tm.get();
             b = c.tm.get();
@@ -1072,22 +897,27 @@ double busy_ms(const Ctx& c, uint32_t mask) {
     return total;
 }
 
-// The (a) items' evaluation: the two trace lists (camera, light connections), then per slot the rest.
-template <int FX>
-void launch_eval_a_fx(int grid, int grid_slots, hipStream_t sm, const DScene& sc, const Paths& S, const DCam& cam,
-                      const Bdpt& B, const Bdpt& R, const BItems& I, int n, const uint32_t* totals) {
-    k_bdpt_eval_a<FX, 0><<<grid, BLOCK, 0, sm>>>(sc, S, cam, B, R, I, n, totals);
-    k_bdpt_eval_a<FX, 1><<<grid, BLOCK, 0, sm>>>(sc, S, cam, B, R, I, n, totals);
-    k_bdpt_eval_a<FX, 2><<<grid_slots, BLOCK, 0, sm>>>(sc, S, cam, B, R, I, n, totals);
+// Feature-class dispatch (DScene::full: 0 lean, 1 full, 2 full + textures): f(FX) with FX an
+// integral_constant, as by_stack_class below.
+template <typename F>
+void by_fx(int fx, F&& f) {
+    if (fx == 2)
+        f(std::integral_constant<int, 2>{});
+    else if (fx)
+        f(std::integral_constant<int, 1>{});
+    else
+        f(std::integral_constant<int, 0>{});
 }
+
+// The (a) items' evaluation: the two trace lists (camera, light connections), then per slot the rest.
 void launch_eval_a(int fx, int grid, int grid_slots, hipStream_t sm, const DScene& sc, const Paths& S, const DCam& cam,
                    const Bdpt& B, const Bdpt& R, const BItems& I, int n, const uint32_t* totals) {
-    if (fx == 2)
-        launch_eval_a_fx<2>(grid, grid_slots, sm, sc, S, cam, B, R, I, n, totals);
-    else if (fx)
-        launch_eval_a_fx<1>(grid, grid_slots, sm, sc, S, cam, B, R, I, n, totals);
-    else
-        launch_eval_a_fx<0>(grid, grid_slots, sm, sc, S, cam, B, R, I, n, totals);
+    by_fx(fx, [&](auto FX) {
+        constexpr int fxc = decltype(FX)::value;
+        k_bdpt_eval_a<fxc, 0><<<grid, BLOCK, 0, sm>>>(sc, S, cam, B, R, I, n, totals);
+        k_bdpt_eval_a<fxc, 1><<<grid, BLOCK, 0, sm>>>(sc, S, cam, B, R, I, n, totals);
+        k_bdpt_eval_a<fxc, 2><<<grid_slots, BLOCK, 0, sm>>>(sc, S, cam, B, R, I, n, totals);
+    });
 }
 
 // Stack-class dispatch (launch.h STACK_CLASSES).
@@ -1114,14 +944,13 @@ void launch_trav(Ctx& c, uint64_t count, F&& f, hipStream_t stream = nullptr, bo
     const bool lds = c.o.lds && c.sc.hot_bytes > 0;
     const bool top = !lds && allow_top && c.o.top && c.sc.top_bytes > 0;
     const int grid_full = ceil_div(count, BLOCK);
-    TravLaunch l{lds ? std::min(grid_full, c.o.lds_grid) : grid_full, lds ? (size_t)c.sc.hot_bytes : 0, lds,
-                 c.sc.full, stream ? stream : c.stream};
-    const hipStream_t ss[4] = {c.stream, c.stream2, c.stream3, c.stream4};
+    TravLaunch l{lds ? std::min(grid_full, (int)c.o.lds_grid) : grid_full, lds ? (size_t)c.sc.hot_bytes : 0, lds,
+                 c.sc.full, stream ? stream : c.streams[0]};
     for (int i = 0; i < 4; ++i)
-        if (l.sm == ss[i]) l.args = c.bargs + i;
+        if (l.sm == c.streams[i]) l.args = c.bargs + i;
     if (top) {
         l.top = true;
-        l.grid = std::min(ceil_div(count, TOP_BLOCK), c.o.top_grid);
+        l.grid = std::min(ceil_div(count, TOP_BLOCK), (int)c.o.top_grid);
         l.shm = c.sc.top_shm;
     }
     by_stack_class(c.sc.stack_class, [&](auto K) { f(K, l); });
@@ -1152,7 +981,7 @@ void alloc_pass_set(Ctx& c, Paths& Q, int k, int N, lumo_status& st) {
     }
 }
 // Ray sorting buffers of pass set k (none when the option is off)
-int ray_sort_mode(const Ctx& c) { return c.o.ray_sort >= 0 ? c.o.ray_sort : (c.sc.stack_class >= 32 ? 1 : 0); }
+int ray_sort_mode(const Ctx& c) { return c.o.ray_sort >= 0 ? (int)c.o.ray_sort : (c.sc.stack_class >= 32 ? 1 : 0); }
 // keys and walk order (cap each) and the counting sort's workspace (scan.h RS_WORDS), zeroed here
 // and by every sort's last block
 void alloc_sort(Ctx& c, HitQ& hq, int k, lumo_status& st) {
@@ -1187,6 +1016,18 @@ size_t split_set_bytes(const Paths& S, int N, int ns) {
            (S.hq.keys ? S.hq.cap * 8 + RS_WORDS * 4 : 0);  // the set's ray-sort keys, order and workspace
 }
 
+// Error returns of the multi-stream schedulers: work already queued on the other streams may still
+// use the buffers the next call re-initialises on stream 0, so every stream is drained before the
+// error is reported.
+struct JoinOnError {
+    Ctx& c;
+    bool ok = false;
+    ~JoinOnError() {
+        if (ok) return;
+        for (int i : {1, 2, 3, 0})
+            if (c.streams[i]) (void)hipStreamSynchronize(c.streams[i]);
+    }
+};
 
 // Pipelined passes (n_shadow == 1, fused bounces).  Russian roulette reads the pass's adaptive
 // delta only from depth RR_DEPTH on (path_trace.rs:60-69), and that delta needs the previous
@@ -1209,24 +1050,14 @@ size_t split_set_bytes(const Paths& S, int N, int ns) {
 // is the one the sequential loop performs, in the same order: bit-identical.
 lumo_status render_pipelined(Ctx& c, Paths& S, const Tasks& T, Dump& D, int dump_p, int N, int n_tasks, int dim_stride,
                              uint64_t max_samples, uint64_t max_P, int M, lumo_status& st) {
-    const int NA = std::min(std::max(c.o.pipeline, 1), 3), NSETS = NA + 1;
-    // On an error return, work already queued on the other streams may still use the buffers the
-    // next call re-initialises on stream 0: drain every stream before reporting the error.
-    struct JoinOnError {
-        Ctx& c;
-        bool ok = false;
-        ~JoinOnError() {
-            if (ok) return;
-            for (hipStream_t s : {c.stream2, c.stream3, c.stream4, c.stream})
-                if (s) (void)hipStreamSynchronize(s);
-        }
-    } join{c};
+    const int NA = std::min(std::max((int)c.o.pipeline, 1), 3), NSETS = NA + 1;
+    JoinOnError join{c};
     Paths P3[4] = {S, S, S, S};
     for (int k = 1; k < NSETS; ++k) alloc_pass_set(c, P3[k], k, N * M, st);  // M passes' outputs and paths
     if (st) return st;
-    hipStream_t As[3] = {c.stream, c.stream3, c.stream4};
-    hipStream_t B = c.stream2;
-    hipStream_t F = NA <= 2 ? c.stream4 : B;  // the films (four streams: the device's hardware queues)
+    hipStream_t As[3] = {c.streams[0], c.streams[2], c.streams[3]};
+    hipStream_t B = c.streams[1];
+    hipStream_t F = NA <= 2 ? c.streams[3] : B;  // the films (four streams: the device's hardware queues)
     // each set's counters start zeroed; from then on every unit's last ring zeroes its set's counters
     {
         ZeroList z;
@@ -1246,12 +1077,12 @@ lumo_status render_pipelined(Ctx& c, Paths& S, const Tasks& T, Dump& D, int dump
     // (a rank's share of a multi-GPU run) the RR bounce goes to the tail kernel too, so the head
     // stream never waits for the previous pass's ring (362^2: 509 -> 434 ms).  Merged units
     // (M > 1) always stop before it.
-    int heads = c.o.heads > 0 ? c.o.heads : (N >= (1 << 21) ? RR_DEPTH + 1 : RR_DEPTH);
+    int heads = c.o.heads > 0 ? (int)c.o.heads : (N >= (1 << 21) ? RR_DEPTH + 1 : RR_DEPTH);
     if (M > 1) heads = std::min(heads, RR_DEPTH);
     c.sched.head_streams = NA;
     c.sched.head_bounces = heads;
     c.sched.merged_passes = M;
-    c.sched.tail_bounces = c.o.tail_bounces >= 0 ? c.o.tail_bounces : (M == 1 ? 2 : 0);
+    c.sched.tail_bounces = c.o.tail_bounces >= 0 ? (int)c.o.tail_bounces : (M == 1 ? 2 : 0);
     const int gN = ceil_div(N, BLOCK);
     const uint64_t units = (max_samples + (uint64_t)M - 1) / (uint64_t)M;
     for (uint64_t u = 0; u < units; ++u) {
@@ -1391,7 +1222,7 @@ void issue_split_bounce(Ctx& c, Paths& S, const Tasks& T, const QState& cur, con
     // made C3's 1/8 share 720 -> 1 300-2 460 ms at thresholds 2^12-2^16: rejected, round 5)
     // (launched only once the last count the host has seen is below 4x the threshold:
     // before that the bounce kernels get threshold 0 and take every path)
-    const uint32_t skip = (allow_tail && ns == 1 && (uint64_t)ub < 4ull * c.o.tail_below) ? c.o.tail_below : 0u;
+    const uint32_t skip = (allow_tail && ns == 1 && (uint64_t)ub < 4ull * c.o.tail_below) ? (uint32_t)c.o.tail_below : 0u;
     if (skip > 0) {
         StageTimer tm(c, c.o.timing, ST_RESOLVE, sm);
         launch_trav(c, std::min(ub, skip), [&](auto K, const TravLaunch& l) {
@@ -1426,22 +1257,14 @@ void issue_split_bounce(Ctx& c, Paths& S, const Tasks& T, const QState& cur, con
         const int g = ceil_div(ub, BLOCK);
         if (ns > 1) {  // NEE pairs by k_nee_gen, one thread per pair
             const int gp = std::min(ceil_div((uint64_t)ub * (uint32_t)ns, BLOCK), 1 << 16);
-            if (c.sc.full == 2) {
-                k_shade_q<2, true><<<g, BLOCK, 0, sm>>>(c.sc, S, T, cur, nxt, skip);
-                k_nee_gen<2><<<gp, BLOCK, 0, sm>>>(c.sc, S);
-            } else if (c.sc.full) {
-                k_shade_q<1, true><<<g, BLOCK, 0, sm>>>(c.sc, S, T, cur, nxt, skip);
-                k_nee_gen<1><<<gp, BLOCK, 0, sm>>>(c.sc, S);
-            } else {
-                k_shade_q<0, true><<<g, BLOCK, 0, sm>>>(c.sc, S, T, cur, nxt, skip);
-                k_nee_gen<0><<<gp, BLOCK, 0, sm>>>(c.sc, S);
-            }
-        } else if (c.sc.full == 2) {
-            k_shade_q<2, false><<<g, BLOCK, 0, sm>>>(c.sc, S, T, cur, nxt, skip);
-        } else if (c.sc.full) {
-            k_shade_q<1, false><<<g, BLOCK, 0, sm>>>(c.sc, S, T, cur, nxt, skip);
+            by_fx(c.sc.full, [&](auto FX) {
+                k_shade_q<decltype(FX)::value, true><<<g, BLOCK, 0, sm>>>(c.sc, S, T, cur, nxt, skip);
+                k_nee_gen<decltype(FX)::value><<<gp, BLOCK, 0, sm>>>(c.sc, S);
+            });
         } else {
-            k_shade_q<0, false><<<g, BLOCK, 0, sm>>>(c.sc, S, T, cur, nxt, skip);
+            by_fx(c.sc.full, [&](auto FX) {
+                k_shade_q<decltype(FX)::value, false><<<g, BLOCK, 0, sm>>>(c.sc, S, T, cur, nxt, skip);
+            });
         }
     }
     {
@@ -1491,15 +1314,7 @@ void issue_split_bounce(Ctx& c, Paths& S, const Tasks& T, const QState& cur, con
 lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int n_tasks, int dim_stride,
                                    uint64_t max_samples, uint64_t max_P, bool fused_now, int K, int G, int M,
                                    const std::vector<int32_t>& first, uint64_t& bounces, lumo_status& st) {
-    struct JoinOnError {
-        Ctx& c;
-        bool ok = false;
-        ~JoinOnError() {
-            if (ok) return;
-            for (hipStream_t s : {c.stream2, c.stream3, c.stream4, c.stream})
-                if (s) (void)hipStreamSynchronize(s);
-        }
-    } join{c};
+    JoinOnError join{c};
     const int ns = c.sc.n_shadow;
     G = std::max(1, std::min(G, std::min(K, n_tasks)));
     // groups of consecutive tasks, about N / G slots each
@@ -1517,23 +1332,22 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
         alloc_split_set(c, P[k], S, k, ns, st);
     }
     if (st) return st;
-    hipStream_t Ss[4] = {c.stream, c.stream2, c.stream3, c.stream4};
     {
         ZeroList z;
         for (int k = 1; k < K; ++k) z.add(P[k].counts, sizeof(uint32_t) * CNT_N);
-        if (z.n) k_zero_list<<<1, BLOCK, 0, Ss[0]>>>(z);
+        if (z.n) k_zero_list<<<1, BLOCK, 0, c.streams[0]>>>(z);
     }
     for (int k = 0; k < 4; ++k) {
-        HIPCHK(hipEventRecord(c.pass_ev[k], Ss[0]));
-        HIPCHK(hipEventRecord(c.film_ev[k], Ss[0]));
+        HIPCHK(hipEventRecord(c.pass_ev[k], c.streams[0]));
+        HIPCHK(hipEventRecord(c.film_ev[k], c.streams[0]));
     }
     // The render's setup (task and pixel tables, seeds, sampler permutations, the initial ring) and
     // the sets' counter zeroing ran on stream 0: every other stream waits for them before its first
     // unit (a pass-0 unit waits for nothing else).  Without this wait a unit on another stream
     // could start on stale counters and tables: found by poisoning fresh buffers (LUMO_POISON).
-    for (int k = 1; k < K; ++k) HIPCHK(hipStreamWaitEvent(Ss[k], c.pass_ev[0], 0));
+    for (int k = 1; k < K; ++k) HIPCHK(hipStreamWaitEvent(c.streams[k], c.pass_ev[0], 0));
     const int SEG = Ctx::SNAP_RING / 4;  // snapshot slots per set
-    const int ahead = std::max(1, std::min(c.o.bounce_ahead, SEG - 1));
+    const int ahead = std::max(1, std::min((int)c.o.bounce_ahead, SEG - 1));
     // A unit's bounce loops: seg -1 the merged head (mu > 1), then seg m = its pass m (a one-pass unit
     // starts at seg 0 with its head included).  Snapshots are numbered over the whole unit; those of an
     // earlier segment are consumed for the statistics only.
@@ -1554,7 +1368,7 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
         const int set = (int)(next % K), g = (int)(next % G);
         const uint64_t pass0 = (next / G) * (uint64_t)M;
         const int mu = (int)std::min<uint64_t>((uint64_t)M, max_samples - pass0);
-        hipStream_t sm = Ss[set];
+        hipStream_t sm = c.streams[set];
         const int s0 = first[t_lo[g]], s1 = first[t_hi[g]];
         if (pass0 > 0) HIPCHK(hipStreamWaitEvent(sm, c.cam_ev[(next - G) % K], 0));  // sampler state per slot
         {
@@ -1571,7 +1385,7 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
     };
     auto ready = [&](const PS& ps) { return ps.waited || finished[ps.g] >= ps.pass0; };
     auto wait_prev = [&](PS& ps) -> lumo_status {  // unit (g, u - 1)'s last ring, already issued
-        if (!ps.waited) HIPCHK(hipStreamWaitEvent(Ss[ps.set], c.pass_ev[(ps.unit - G) % K], 0));
+        if (!ps.waited) HIPCHK(hipStreamWaitEvent(c.streams[ps.set], c.pass_ev[(ps.unit - G) % K], 0));
         ps.waited = true;
         return LUMO_OK;
     };
@@ -1599,7 +1413,7 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
         return ps.mu > 1 || ps.seg_issued >= RR_DEPTH || tail_possible(ps);
     };
     auto issue = [&](PS& ps) -> lumo_status {
-        hipStream_t sm = Ss[ps.set];
+        hipStream_t sm = c.streams[ps.set];
         if (needs_delta(ps)) {
             const lumo_status w = wait_prev(ps);
             if (w) return w;
@@ -1637,7 +1451,7 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
     };
     // the merged head is over (RR_DEPTH bounces, or no path left): its queue split by pass
     auto split = [&](PS& ps) -> lumo_status {
-        hipStream_t sm = Ss[ps.set];
+        hipStream_t sm = c.streams[ps.set];
         const Paths& Q = P[ps.set];
         ZeroList z;
         z.add(Q.counts + CNT_N, sizeof(uint32_t) * CNT_N * (size_t)ps.mu);
@@ -1656,7 +1470,7 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
     // the ring of the segment's pass (task.rs:28-69, from the pass's final radiance); after the
     // unit's last pass its film (after the group's previous film: the film accumulates in pass order)
     auto finish = [&](PS& ps) -> lumo_status {
-        hipStream_t sm = Ss[ps.set];
+        hipStream_t sm = c.streams[ps.set];
         const Paths& Q = P[ps.set];
         const int t0 = t_lo[ps.g], t1 = t_hi[ps.g], s0 = first[t0], s1 = first[t1];
         const lumo_status w = wait_prev(ps);
@@ -1753,26 +1567,32 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
     }
     // the results are copied on stream 0: after every set's last unit
     for (int k = 1; k < K; ++k) {
-        HIPCHK(hipStreamWaitEvent(Ss[0], c.pass_ev[k], 0));
-        HIPCHK(hipStreamWaitEvent(Ss[0], c.film_ev[k], 0));
+        HIPCHK(hipStreamWaitEvent(c.streams[0], c.pass_ev[k], 0));
+        HIPCHK(hipStreamWaitEvent(c.streams[0], c.film_ev[k], 0));
     }
     join.ok = true;
     return LUMO_OK;
 }
 
-// BDPT in task groups (render_impl, bidirectional integrator): the tasks are cut into G groups of
-// consecutive tasks, each rendered as its own chain of passes on its own stream, with its own view
+// BDPT, the one pass body of the bidirectional integrator (bdpt.h): light subpaths, then camera
+// subpaths, bounce by bounce through k_closest + k_bdpt_step (k_bdpt_tail ahead of them once few
+// subpaths are alive); re-runs of the samples that did not fit; connection items; fold; film, ring
+// and splat taps.  Stage slots: walks = CLOSEST + SHADE, re-runs + fold = RESOLVE.
+//
+// The tasks are cut into G groups of consecutive tasks (G = 1: one chain on stream 0, also what a
+// path dump runs, its Dump `D` written by the film kernels), each rendered as its own chain of
+// passes on its own stream, with its own view
 // of the per-slot buffers (offset to its first slot), its own walk queues, counters, redo list and
 // store, connection item lists and scan storage.  lumo's adaptive Russian roulette reads a task's
 // delta in the walks (path_gen.rs:133-145) and the delta of pass p needs that task's ring of pass
-// p - 1 (task.rs:28-53): within a group the passes follow one another on the group's stream, as in
-// the sequential loop; groups share nothing but the scene, the task table and the splat film
+// p - 1 (task.rs:28-53): within a group the passes follow one another on the group's stream;
+// groups share nothing but the scene, the task table and the splat film
 // (atomics: its sum order is unspecified anyway), so their chains overlap freely: one group's
 // latency-bound walk tails and connection traces run beside the other's item kernels.  The host
 // drives every group's pass as a state machine (walk bounces issued `ahead` of their count
 // snapshots; the item totals read back through pinned memory when their event completes), so it
 // waits for nothing a group needs.  Every per-sample operation, every item and every film / ring
-// sum of a task is the sequential loop's, in the same order: bit-identical.  (Per-task splat lists,
+// sum of a task is the same for every G, in the same order: bit-identical.  (Per-task splat lists,
 // the test / library path, are read back with a blocking wait per pass.)
 enum BdPhase { BD_LIGHT = 0, BD_CAMERA, BD_TOTALS, BD_DONE };
 struct BdGroup {
@@ -1809,22 +1629,14 @@ VStore vstore_part(const VStore& v, int s0, int n) {
     return VStore{v.d + o * VD_N, v.i + o * VI_N, v.V, n, v.m + 2 * o, v.mf + o};
 }
 
-lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Bdpt& B, const BItems& BI, int N, int n_tasks,
-                               int dim_stride, uint64_t max_samples, uint64_t max_P, int G,
-                               const std::vector<int32_t>& first, uint32_t* items_total, bool splat_lists, double* dfilm, uint32_t* tap_cnt,
-                               uint32_t* tap_off, lumo_tile_result* out, std::vector<uint64_t>& n_splats,
-                               uint64_t& bounces, lumo_status& st) {
-    struct JoinOnError {
-        Ctx& c;
-        bool ok = false;
-        ~JoinOnError() {
-            if (ok) return;
-            for (hipStream_t s : {c.stream2, c.stream3, c.stream4, c.stream})
-                if (s) (void)hipStreamSynchronize(s);
-        }
-    } join{c};
+lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, int dump_p, const Bdpt& B,
+                               const BItems& BI, int N, int n_tasks, int dim_stride, uint64_t max_samples,
+                               uint64_t max_P, int G, const std::vector<int32_t>& first, uint32_t* items_total,
+                               bool splat_lists, double* dfilm, uint32_t* tap_cnt, uint32_t* tap_off,
+                               lumo_tile_result* out, std::vector<uint64_t>& n_splats, uint64_t& bounces,
+                               lumo_status& st) {
+    JoinOnError join{c};
     G = std::max(1, std::min(std::min(G, 4), n_tasks));
-    hipStream_t Ss[4] = {c.stream, c.stream2, c.stream3, c.stream4};
     std::vector<BdGroup> gr(G);
     const int V = B.lp.V, VR = BDPT_MAX_DEPTH + 1;
     for (int g = 0, t = 0; g < G; ++g) {  // groups of consecutive tasks, about N / G slots each
@@ -1836,7 +1648,7 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Bdpt& B, 
         q.t1 = t;
         q.s0 = first[q.t0];
         q.n = first[q.t1] - q.s0;
-        q.sm = Ss[g];
+        q.sm = c.streams[g];
         const size_t o = (size_t)q.s0;
         Paths& P = q.S;
         P = S;
@@ -1906,12 +1718,13 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Bdpt& B, 
     }
     if (st) return st;
     // every group stream waits for the render's setup on stream 0 (tables, seeds, zeroing, ring)
-    HIPCHK(hipEventRecord(c.pass_ev[0], Ss[0]));
-    for (int g = 1; g < G; ++g) HIPCHK(hipStreamWaitEvent(Ss[g], c.pass_ev[0], 0));
+    HIPCHK(hipEventRecord(c.pass_ev[0], c.streams[0]));
+    for (int g = 1; g < G; ++g) HIPCHK(hipStreamWaitEvent(c.streams[g], c.pass_ev[0], 0));
     const int SEG = Ctx::SNAP_RING / 4;
-    const int ahead = std::max(1, std::min(c.o.bounce_ahead, SEG - 1));
+    const int ahead = std::max(1, std::min((int)c.o.bounce_ahead, SEG - 1));
     const int fx = c.sc.full;
-    const int walk_sort = c.o.ray_sort > 0 ? c.o.ray_sort : 0;  // walks: on request (LUMO_OPT_RAY_SORT 1 / 2)
+    // walks: sorted on request (LUMO_OPT_RAY_SORT 1 / 2), and only with concurrent groups
+    const int walk_sort = G > 1 && c.o.ray_sort > 0 ? (int)c.o.ray_sort : 0;
     auto start_walk = [&](BdGroup& q, int phase) {
         q.phase = phase;
         q.walk = 0;
@@ -1920,19 +1733,17 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Bdpt& B, 
         q.done = false;
     };
     auto start_pass = [&](BdGroup& q) -> lumo_status {
+        // a path dump (one task, one group): the delta this pass's Russian roulette reads
+        if (D.delta) HIPCHK(hipMemcpyAsync(D.delta + q.pass, T.delta, sizeof(double), hipMemcpyDeviceToDevice, q.sm));
         {
             StageTimer tm(c, c.o.timing, ST_CAMERA, q.sm);
             k_camera<false><<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(T, q.S, c.cam, q.n, dim_stride, (uint32_t)q.pass, 0,
                                                                        1, 0);
         }
         k_zero_counts<<<1, 64, 0, q.sm>>>(q.S.counts, q.B.redo_count);  // drop k_camera's queue; no re-runs yet
-        const int g = ceil_div(q.n, BLOCK);
-        if (fx == 2)
-            k_bdpt_light_init<2><<<g, BLOCK, 0, q.sm>>>(c.sc, q.S, q.B, q.I, q.n);
-        else if (fx)
-            k_bdpt_light_init<1><<<g, BLOCK, 0, q.sm>>>(c.sc, q.S, q.B, q.I, q.n);
-        else
-            k_bdpt_light_init<0><<<g, BLOCK, 0, q.sm>>>(c.sc, q.S, q.B, q.I, q.n);
+        by_fx(fx, [&](auto FX) {
+            k_bdpt_light_init<decltype(FX)::value><<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(c.sc, q.S, q.B, q.I, q.n);
+        });
         HIPCHK(hipGetLastError());
         start_walk(q, BD_LIGHT);
         return LUMO_OK;
@@ -1945,7 +1756,7 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Bdpt& B, 
         int32_t* qb = (q.walk & 1) ? q.S.q0 : q.S.q1;
         const uint32_t ub = q.ub;
         k_bounce_begin<<<1, 64, 0, q.sm>>>(q.S.counts, q.S.tcount + TC_HEADQ);
-        const uint32_t skip = (uint64_t)ub < 4ull * c.o.bdpt_tail ? c.o.bdpt_tail : 0u;
+        const uint32_t skip = (uint64_t)ub < 4ull * c.o.bdpt_tail ? (uint32_t)c.o.bdpt_tail : 0u;
         if (walk_sort && skip == 0 && ub >= kSortMin) {  // the walk's rays sorted (lane order only)
             StageTimer tm(c, c.o.timing, ST_CLOSEST, q.sm);
             const size_t nq = (size_t)q.n;
@@ -2072,12 +1883,10 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Bdpt& B, 
             }
             StageTimer tm(c, c.o.timing, ST_BD_PATHS, q.sm);
             const int grid = std::min(ceil_div(tot[1], BLOCK), 1 << 16);
-            if (fx == 2)
-                k_bdpt_paths<2><<<grid, BLOCK, 0, q.sm>>>(c.sc, q.S, c.cam, q.B, q.R, q.I, q.n, q.totals);
-            else if (fx)
-                k_bdpt_paths<1><<<grid, BLOCK, 0, q.sm>>>(c.sc, q.S, c.cam, q.B, q.R, q.I, q.n, q.totals);
-            else
-                k_bdpt_paths<0><<<grid, BLOCK, 0, q.sm>>>(c.sc, q.S, c.cam, q.B, q.R, q.I, q.n, q.totals);
+            by_fx(fx, [&](auto FX) {
+                k_bdpt_paths<decltype(FX)::value><<<grid, BLOCK, 0, q.sm>>>(c.sc, q.S, c.cam, q.B, q.R, q.I, q.n,
+                                                                           q.totals);
+            });
         }
         {
             StageTimer tm(c, c.o.timing, ST_RESOLVE, q.sm);
@@ -2087,12 +1896,12 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Bdpt& B, 
         const int s1 = q.s0 + q.n;
         if (max_P <= BLOCK) {  // film and ring from the render's whole per-slot view, this group's tasks
             StageTimer tm(c, c.o.timing, ST_FILM, q.sm);
-            k_finish_film<<<q.t1 - q.t0, BLOCK, 0, q.sm>>>(c.sc, S, T, c.cam, (uint32_t)q.pass, Dump{}, 0, c.tone_map,
+            k_finish_film<<<q.t1 - q.t0, BLOCK, 0, q.sm>>>(c.sc, S, T, c.cam, (uint32_t)q.pass, D, dump_p, c.tone_map,
                                                             c.tone_arg, q.t0, 1, 0);
         } else {
             {
                 StageTimer tm(c, c.o.timing, ST_FINISH, q.sm);
-                k_finish<<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(c.sc, S, c.cam, s1, (uint32_t)q.pass, Dump{}, 0,
+                k_finish<<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(c.sc, S, c.cam, s1, (uint32_t)q.pass, D, dump_p,
                                                                   c.tone_map, c.tone_arg, q.s0);
             }
             StageTimer tm(c, c.o.timing, ST_FILM, q.sm);
@@ -2180,8 +1989,8 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Bdpt& B, 
     }
     // the results are copied on stream 0: after every group's last pass
     for (int g = 1; g < G; ++g) {
-        HIPCHK(hipEventRecord(c.pass_ev[g], Ss[g]));
-        HIPCHK(hipStreamWaitEvent(Ss[0], c.pass_ev[g], 0));
+        HIPCHK(hipEventRecord(c.pass_ev[g], c.streams[g]));
+        HIPCHK(hipStreamWaitEvent(c.streams[0], c.pass_ev[g], 0));
     }
     join.ok = true;
     return LUMO_OK;
@@ -2229,7 +2038,7 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         ns == 1 && (c.o.fused < 0 ? (c.o.lds && c.sc.hot_bytes > 0 && fused_fits) : c.o.fused != 0);
     const bool pipe = !bdpt && fused_now && c.o.pipeline;
     // the split schedule's pipeline (render_split_pipelined), when the free HBM allows (below)
-    const uint64_t split_units = max_samples * (uint64_t)std::max(1, std::min(c.o.split_groups, (int)n_tasks));
+    const uint64_t split_units = max_samples * (uint64_t)std::max(1, std::min((int)c.o.split_groups, (int)n_tasks));
     const bool split_try = !bdpt && !pipe && !dump_host && c.o.pipeline && c.o.split_pipe > 1 && split_units > 1;
     int M = 1;
     if (pipe || split_try) {  // merged passes: units of about kMergeTarget paths
@@ -2238,7 +2047,7 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         // frame slower (M = 2 / 4 / 8: 723 -> 761 / 807 / 812 ms; the unit's large head launches
         // hold the CUs while the latency-bound per-pass bounces of the group's chain wait; round 5)
         if (split_try) M = 1;
-        if (c.o.merge > 0) M = c.o.merge;
+        if (c.o.merge > 0) M = (int)c.o.merge;
         M = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)M, max_samples));
         if ((uint64_t)N * (uint64_t)M > ((uint64_t)1 << 30)) M = 1;
     }
@@ -2326,13 +2135,12 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         D.depth = wbuf<unsigned long long>(c, W_DUMP_DEPTH, m, st);
         D.delta = wbuf<double>(c, W_DUMP_DELTA, dump_samples, st);
     }
-    Bdpt B{}, BR{};  // BR: redo storage for subpaths longer than B holds
-    BItems BI{};     // connection work items
+    Bdpt B{};     // subpath vertices (the task groups add their redo lists and stores, render_bdpt_groups)
+    BItems BI{};  // connection work items
     uint32_t* items_total = nullptr;
     bool splat_lists = true;
     uint32_t* tap_cnt = nullptr;
     uint32_t* tap_off = nullptr;
-    uint64_t* tap_ranges = nullptr;
     double* dfilm = nullptr;
     size_t film_n = 0;
     if (bdpt) {
@@ -2344,10 +2152,7 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         B.sp = SplatStore{wbuf<double>(c, W_BD_SP, (size_t)10 * V * N, st), wbuf<int32_t>(c, W_BD_SPN, N, st), V, N};
         B.overflow = wbuf<uint32_t>(c, W_BD_OVF, 8, st);  // (overflow, redo count) per task group
         B.redo_count = B.overflow + 1;
-        B.redo_cap = (uint32_t)std::min(N, 4096);
-        B.redo_list = wbuf<int32_t>(c, W_BD_REDO_LIST, B.redo_cap, st);
         B.redo_index = wbuf<int32_t>(c, W_BD_REDO_INDEX, N, st);
-        const int VR = BDPT_MAX_DEPTH + 1, NR = (int)B.redo_cap;  // storage for lumo's deepest subpath
         B.draws = wbuf<double>(c, W_BD_DRAWS, (size_t)5 * V * N, st);
         B.ok = wbuf<int32_t>(c, W_BD_OK, (size_t)V * N, st);
         BI.nl = wbuf<int32_t>(c, W_BD_NL, N, st);
@@ -2363,20 +2168,11 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         BI.rng0 = wbuf<uint64_t>(c, W_BD_RNG0, 2 * (size_t)N, st);
         BI.lam0 = wbuf<double>(c, W_BD_LAM0, 4 * (size_t)N, st);
         items_total = wbuf<uint32_t>(c, W_BD_ITOTAL, 32, st);  // (a), (b) and the item lists' counts per task group
-        BR = B;
-        BR.lp = VStore{wbuf<double>(c, W_BDR_LD, (size_t)VD_N * VR * NR, st), wbuf<int32_t>(c, W_BDR_LI, (size_t)VI_N * VR * NR, st), VR, NR,
-                       wbuf<double>(c, W_BDR_LM, (size_t)2 * VR * NR, st), wbuf<int32_t>(c, W_BDR_LMF, (size_t)VR * NR, st)};
-        BR.cp = VStore{wbuf<double>(c, W_BDR_CD, (size_t)VD_N * VR * NR, st), wbuf<int32_t>(c, W_BDR_CI, (size_t)VI_N * VR * NR, st), VR, NR,
-                       wbuf<double>(c, W_BDR_CM, (size_t)2 * VR * NR, st), wbuf<int32_t>(c, W_BDR_CMF, (size_t)VR * NR, st)};
-        BR.sp = SplatStore{wbuf<double>(c, W_BDR_SP, (size_t)10 * VR * NR, st), wbuf<int32_t>(c, W_BDR_SPN, NR, st), VR, NR};
-        BR.draws = wbuf<double>(c, W_BDR_DRAWS, (size_t)5 * VR * NR, st);
-        BR.ok = wbuf<int32_t>(c, W_BDR_OK, (size_t)VR * NR, st);
         for (size_t i = 0; i < n_tasks && out; ++i) splat_lists = splat_lists && out[i].splats != nullptr;
         if (!out) splat_lists = false;
         if (splat_lists) {
             tap_cnt = wbuf<uint32_t>(c, W_BD_CNT, N, st);
             tap_off = wbuf<uint32_t>(c, W_BD_OFF, N, st);
-            tap_ranges = wbuf<uint64_t>(c, W_BD_RANGES, n_tasks + 1, st);
         } else if (c.splat_film) {
             film_n = (size_t)3 * (size_t)c.cam.width * (size_t)c.cam.height;
             dfilm = wbuf<double>(c, W_BD_FILM, film_n, st);
@@ -2386,10 +2182,8 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
     }
     if (st) return st;
 
-    hipStream_t sm = c.stream;
+    hipStream_t sm = c.streams[0];
     std::vector<uint64_t> n_splats(n_tasks, 0);
-    std::vector<lumo_splat> taps_h;
-    std::vector<uint64_t> ranges_h(n_tasks + 1);
     HIPCHK(hipMemcpyAsync(T.t, tasks, sizeof(lumo_tile_task) * n_tasks, hipMemcpyHostToDevice, sm));
     HIPCHK(hipMemcpyAsync(T.first, first.data(), sizeof(int32_t) * (n_tasks + 1), hipMemcpyHostToDevice, sm));
     HIPCHK(hipMemcpyAsync(S.task, task_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, sm));
@@ -2426,7 +2220,7 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
     // as an upper bound (counts never grow within a pass); the kernels read the exact counts from
     // device memory.  A pass ends once a snapshot shows no path alive; the bounces enqueued past
     // that point see empty queues and exit at once.
-    const int ahead = c.o.bounce_ahead;
+    const int ahead = (int)c.o.bounce_ahead;
     if (pipe) {
         const lumo_status ps = render_pipelined(c, S, T, D, dump_p, N, (int)n_tasks, dim_stride, max_samples, max_P, M, st);
         if (ps) return ps;
@@ -2439,205 +2233,81 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         const size_t per_set = split_set_bytes(S, (int)NV, ns);
         const size_t margin = (size_t)8 << 30;
         const uint64_t units = (max_samples + (uint64_t)M - 1) / (uint64_t)M *
-                               (uint64_t)std::max(1, std::min(c.o.split_groups, (int)n_tasks));
+                               (uint64_t)std::max(1, std::min((int)c.o.split_groups, (int)n_tasks));
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            K = std::min(std::min(c.o.split_pipe, 4), (int)std::min<uint64_t>(units, 4));
+            K = std::min(std::min((int)c.o.split_pipe, 4), (int)std::min<uint64_t>(units, 4));
             while (K > 1 && (size_t)(K - 1) * per_set + margin > free_b + c.split_sets_bytes) K--;
         }
     }
     if (K > 1) {
         c.sched.schedule = LUMO_SCHED_SPLIT_PIPELINE;
         c.sched.units_in_flight = K;
-        c.sched.task_groups = std::max(1, std::min(c.o.split_groups, std::min(K, (int)n_tasks)));
+        c.sched.task_groups = std::max(1, std::min((int)c.o.split_groups, std::min(K, (int)n_tasks)));
         c.sched.merged_passes = M;
         const lumo_status ps = render_split_pipelined(c, S, T, N, (int)n_tasks, dim_stride, max_samples, max_P,
-                                                      fused_now, K, c.o.split_groups, M, first, bounces, st);
+                                                      fused_now, K, (int)c.o.split_groups, M, first, bounces, st);
         if (ps) return ps;
         if (st) return st;
         c.split_sets_bytes = std::max(c.split_sets_bytes, (size_t)(K - 1) * split_set_bytes(S, (int)NV, ns));
     }
-    // BDPT: task groups as concurrent pass chains (render_bdpt_groups)
-    const int bd_groups = std::min(std::min(c.o.bdpt_groups, 4), (int)n_tasks);
-    const bool bd_grouped = bdpt && !dump_host && bd_groups > 1;
-    if (bd_grouped) {
-        c.sched.schedule = LUMO_SCHED_BDPT_GROUPS;
-        c.sched.task_groups = bd_groups;
-        c.sched.units_in_flight = bd_groups;
-        const lumo_status ps = render_bdpt_groups(c, S, T, B, BI, N, (int)n_tasks, dim_stride, max_samples, max_P,
-                                                  bd_groups, first, items_total, splat_lists, dfilm, tap_cnt, tap_off,
+    // BDPT: every render runs the task groups' pass body (render_bdpt_groups): concurrent chains of
+    // passes for several tasks; one chain (G = 1, reported as the sequential schedule) for a single
+    // task, on request (LUMO_OPT_BDPT_GROUPS 1) and for a path dump
+    if (bdpt) {
+        const int G = dump_host ? 1 : std::min(std::min((int)c.o.bdpt_groups, 4), (int)n_tasks);
+        if (G > 1) {
+            c.sched.schedule = LUMO_SCHED_BDPT_GROUPS;
+            c.sched.task_groups = G;
+            c.sched.units_in_flight = G;
+        }
+        const lumo_status ps = render_bdpt_groups(c, S, T, D, dump_p, B, BI, N, (int)n_tasks, dim_stride, max_samples,
+                                                  max_P, G, first, items_total, splat_lists, dfilm, tap_cnt, tap_off,
                                                   out, n_splats, bounces, st);
         if (ps) return ps;
         if (st) return st;
     }
-    for (uint64_t pass = 0; pass < ((pipe || K > 1 || bd_grouped) ? 0 : max_samples); ++pass) {
+    // the sequential loop: path tracing without a pipeline
+    for (uint64_t pass = 0; pass < ((bdpt || pipe || K > 1) ? 0 : max_samples); ++pass) {
         if (dump_host) HIPCHK(hipMemcpyAsync(D.delta + pass, T.delta, sizeof(double), hipMemcpyDeviceToDevice, sm));
         // S.counts: zeroed at setup, then by the ring at the end of every pass
         {
             StageTimer tm(c, c.o.timing, ST_CAMERA);
-            if (bdpt)
-                k_camera<false><<<gN, BLOCK, 0, sm>>>(T, S, c.cam, N, dim_stride, (uint32_t)pass, 0, 1, 0);
-            else
-                k_camera<true><<<gN, BLOCK, 0, sm>>>(T, S, c.cam, N, dim_stride, (uint32_t)pass, 0, 1, 0);
+            k_camera<true><<<gN, BLOCK, 0, sm>>>(T, S, c.cam, N, dim_stride, (uint32_t)pass, 0, 1, 0);
         }
         HIPCHK(hipGetLastError());
-        // Bounce loop over the alive queue (filled by the producer just launched): `step` launches
-        // the bounce's kernels (closest hit, then the integrator's per-hit kernels) for bounce
-        // `b` (its parity selects the ping-pong buffers).  Bounces are enqueued ahead of the host's
+        // Bounce loop over the alive queue (filled by the camera kernel just launched); the parity
+        // of the bounce selects the ping-pong queues.  Bounces are enqueued ahead of the host's
         // knowledge of the counts; see above.
-        auto bounce_loop = [&](auto&& step) -> lumo_status {
-            int32_t* qa = S.q0;
-            int32_t* qb = S.q1;
-            uint32_t ub = (uint32_t)N;  // upper bound on the alive count of the next bounce
-            int issued = 0, consumed = 0;
-            bool done = false;
-            for (;;) {
-                while (consumed < issued) {
-                    hipEvent_t e = c.snap_ev[consumed % Ctx::SNAP_RING];
-                    if (issued - consumed >= ahead) {
-                        HIPCHK(hipEventSynchronize(e));
-                    } else if (hipEventQuery(e) != hipSuccess) {
-                        break;
-                    }
-                    const uint32_t* k = c.snap + CNT_N * (consumed % Ctx::SNAP_RING);
-                    bounces += k[CNT_CUR] > 0 ? 1 : 0;
-                    ub = k[CNT_NEXT];
-                    done = done || ub == 0;
-                    consumed++;
+        uint32_t ub = (uint32_t)N;  // upper bound on the alive count of the next bounce
+        int issued = 0, consumed = 0;
+        bool done = false;
+        for (;;) {
+            while (consumed < issued) {
+                hipEvent_t e = c.snap_ev[consumed % Ctx::SNAP_RING];
+                if (issued - consumed >= ahead) {
+                    HIPCHK(hipEventSynchronize(e));
+                } else if (hipEventQuery(e) != hipSuccess) {
+                    break;
                 }
-                if (done) break;
-                k_bounce_begin<<<1, 64, 0, sm>>>(S.counts, S.tcount + TC_HEADQ);
-                step(ub, issued, qa, qb);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(c.snap + CNT_N * (issued % Ctx::SNAP_RING), S.counts, sizeof(uint32_t) * CNT_N,
-                                      hipMemcpyDeviceToHost, sm));
-                HIPCHK(hipEventRecord(c.snap_ev[issued % Ctx::SNAP_RING], sm));
-                issued++;
-                std::swap(qa, qb);
+                const uint32_t* k = c.snap + CNT_N * (consumed % Ctx::SNAP_RING);
+                bounces += k[CNT_CUR] > 0 ? 1 : 0;
+                ub = k[CNT_NEXT];
+                done = done || ub == 0;
+                consumed++;
             }
-            // The bounces issued past the first empty snapshot see empty queues; nothing waits for
-            // them: the stream orders them before the film kernels launched next (waiting here
-            // left the GPU idle for a host round trip per pass), and their snapshot slots and
-            // events are simply re-recorded by the next pass.
-            return LUMO_OK;
-        };
-        lumo_status bst = LUMO_OK;
-        if (!bdpt) {
-            bst = bounce_loop([&](uint32_t ub, int b, int32_t*, int32_t*) {
-                issue_split_bounce(c, S, T, S.qs[b & 1], S.qs[(b + 1) & 1], ub, sm, fused_now);
-            });
-            if (bst) return bst;
-        } else {
-            // BDPT (bdpt.h): light subpaths, then camera subpaths, bounce by bounce through k_closest
-            // + k_bdpt_step; re-runs of samples that did not fit; connection items; fold.  Stage
-            // slots: walks = CLOSEST + SHADE, items = SHADOW, re-runs + fold = RESOLVE.
-            // once few subpaths are alive, k_bdpt_tail is launched ahead of each bounce and, below
-            // c.o.bdpt_tail paths (the exact count, on the device), runs every remaining walk to its
-            // end in that launch; the bounce kernels then skip (as the path tracer's tail kernel)
-            auto walk_step = [&](int mode) {
-                return [&, mode](uint32_t ub, int, int32_t* qa, int32_t* qb) {
-                    const uint32_t skip = (uint64_t)ub < 4ull * c.o.bdpt_tail ? c.o.bdpt_tail : 0u;
-                    if (skip > 0) {
-                        StageTimer tm(c, c.o.timing, ST_RESOLVE);
-                        launch_trav(c, std::min(ub, skip), [&](auto K, const TravLaunch& l) {
-                            launch_bdpt_tail<decltype(K)::value>(l, c.sc, S, T, B, BI, mode, qa, skip);
-                        });
-                    }
-                    {
-                        StageTimer tm(c, c.o.timing, ST_CLOSEST);
-                        launch_trav(c, ub, [&](auto K, const TravLaunch& l) {
-                            launch_closest<decltype(K)::value>(l, c.sc, S, qa, skip);
-                        });
-                    }
-                    StageTimer tm(c, c.o.timing, ST_SHADE);
-                    by_stack_class(c.sc.stack_class, [&](auto K) {
-                        launch_bdpt_step<decltype(K)::value>(ceil_div(ub, BLOCK), sm, c.sc.full, c.sc, S, T, B, BI, mode, qa, qb,
-                                                             skip);
-                    });
-                };
-            };
-            k_zero_counts<<<1, 64, 0, sm>>>(S.counts, B.redo_count);  // drop k_camera's queue; no re-runs yet
-            if (c.sc.full == 2)
-                k_bdpt_light_init<2><<<gN, BLOCK, 0, sm>>>(c.sc, S, B, BI, N);
-            else if (c.sc.full)
-                k_bdpt_light_init<1><<<gN, BLOCK, 0, sm>>>(c.sc, S, B, BI, N);
-            else
-                k_bdpt_light_init<0><<<gN, BLOCK, 0, sm>>>(c.sc, S, B, BI, N);
-            bst = bounce_loop(walk_step(TR_IMPORTANCE));
-            if (bst) return bst;
-            k_zero_counts<<<1, 64, 0, sm>>>(S.counts, nullptr);
-            k_bdpt_cam_init<<<gN, BLOCK, 0, sm>>>(S, B, BI, c.cam, N);
-            bst = bounce_loop(walk_step(TR_RADIANCE));
-            if (bst) return bst;
-            {
-                StageTimer tm(c, c.o.timing, ST_RESOLVE);
-                launch_trav(c, (uint64_t)B.redo_cap, [&](auto K, const TravLaunch& l) {
-                    launch_bdpt_redo<decltype(K)::value>(l, c.sc, S, T, c.cam, B, BR, BI);
-                });
-            }
-            // connection items: scan the per-slot counts, size the term buffers, one thread per item
-            for (int k = 0; k < 2; ++k) {
-                uint32_t* cnt = k == 0 ? BI.n_a : BI.n_b;
-                uint32_t* off = k == 0 ? BI.off_a : BI.off_b;
-                uint32_t* sums = wbuf<uint32_t>(c, W_BD_SCAN, (size_t)scan_blocks(N), st);
-                if (st) return st;
-                HIPCHK(exclusive_scan(cnt, off, N, sums, sm));
-            }
-            k_bdpt_total<<<1, 64, 0, sm>>>(BI, N, items_total);
-            uint32_t totals[2] = {0, 0};
-            HIPCHK(hipMemcpyAsync(totals, items_total, sizeof(totals), hipMemcpyDeviceToHost, sm));
-            HIPCHK(hipStreamSynchronize(sm));
-            BI.term_a = wbuf<double>(c, W_BD_TERM, 4 * (size_t)std::max(totals[0], 1u), st);
-            BI.term_b = wbuf<double>(c, W_BD_TERMB, 4 * (size_t)std::max(totals[1], 1u), st);
-            BI.blist = wbuf<int32_t>(c, W_BD_VIS, 2 * (size_t)std::max(totals[1], 1u), st);
-            BI.blist_cap = std::max(totals[1], 1u);
-            BI.a_t = wbuf<double>(c, W_BD_AT, std::max(totals[0], 1u), st);
-            BI.a_kind = wbuf<int32_t>(c, W_BD_AKIND, std::max(totals[0], 1u), st);
-            BI.a_obj = wbuf<int32_t>(c, W_BD_AOBJ, std::max(totals[0], 1u), st);
-            BI.a_tri = wbuf<int32_t>(c, W_BD_ATRI, std::max(totals[0], 1u), st);
-            BI.alist = wbuf<int32_t>(c, W_BD_ALIST, 2 * (size_t)std::max(totals[0], 1u), st);
-            BI.alist_cap = std::max(totals[0], 1u);
-            if (st) return st;
-            if (totals[0] > 0) {
-                {
-                    StageTimer tm(c, c.o.timing, ST_BD_TRACE_A);
-                    k_bdpt_alists<<<gN, BLOCK, 0, sm>>>(B, BR, BI, N, items_total);
-                    for (int kind = 0; kind < 2; ++kind)
-                        launch_trav(c, (uint64_t)totals[0], [&](auto K, const TravLaunch& l) {
-                            launch_bdpt_trace_a<decltype(K)::value>(l, c.sc, S, c.cam, B, BR, BI, N, items_total, kind);
-                        });
-                }
-                StageTimer tm(c, c.o.timing, ST_BD_EVAL_A);
-                launch_eval_a(c.sc.full, std::min(ceil_div(totals[0], BLOCK), 1 << 16), gN, sm, c.sc, S, c.cam, B, BR, BI,
-                              N, items_total);
-            }
-            if (totals[1] > 0) {
-                {
-                    StageTimer tm(c, c.o.timing, ST_BD_VIS);
-                    k_bdpt_blists<<<gN, BLOCK, 0, sm>>>(B, BR, BI, N, items_total);
-                    launch_trav(
-                        c, (uint64_t)totals[1],
-                        [&](auto K, const TravLaunch& l) {
-                            launch_bdpt_vis<decltype(K)::value>(l, c.sc, S, B, BR, BI, N, items_total);
-                        },
-                        // textured scenes (fx 2) have no TOP variant: their full-grid launch
-                        nullptr, c.o.bdpt_top != 0 && c.sc.full != 2);
-                }
-                StageTimer tm(c, c.o.timing, ST_BD_PATHS);
-                const int grid = std::min(ceil_div(totals[1], BLOCK), 1 << 16);
-                if (c.sc.full == 2)
-                    k_bdpt_paths<2><<<grid, BLOCK, 0, sm>>>(c.sc, S, c.cam, B, BR, BI, N, items_total);
-                else if (c.sc.full)
-                    k_bdpt_paths<1><<<grid, BLOCK, 0, sm>>>(c.sc, S, c.cam, B, BR, BI, N, items_total);
-                else
-                    k_bdpt_paths<0><<<grid, BLOCK, 0, sm>>>(c.sc, S, c.cam, B, BR, BI, N, items_total);
-            }
-            {
-                StageTimer tm(c, c.o.timing, ST_RESOLVE);
-                k_bdpt_fold<<<gN, BLOCK, 0, sm>>>(S, B, BR, BI, N);
-            }
+            if (done) break;
+            k_bounce_begin<<<1, 64, 0, sm>>>(S.counts, S.tcount + TC_HEADQ);
+            issue_split_bounce(c, S, T, S.qs[issued & 1], S.qs[(issued + 1) & 1], ub, sm, fused_now);
             HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(c.snap + CNT_N * (issued % Ctx::SNAP_RING), S.counts, sizeof(uint32_t) * CNT_N,
+                                  hipMemcpyDeviceToHost, sm));
+            HIPCHK(hipEventRecord(c.snap_ev[issued % Ctx::SNAP_RING], sm));
+            issued++;
         }
-        if (c.o.timing && bdpt) HIPCHK(hipStreamSynchronize(sm));  // BDPT passes have no bounce snapshots
+        // The bounces issued past the first empty snapshot see empty queues; nothing waits for
+        // them: the stream orders them before the film kernels launched next (waiting here
+        // left the GPU idle for a host round trip per pass), and their snapshot slots and
+        // events are simply re-recorded by the next pass.
         if (c.o.timing) resolve_timers(c);
         if (max_P <= BLOCK) {  // one block per tile (lumo's 16x16 tiles)
             StageTimer tm(c, c.o.timing, ST_FILM);
@@ -2658,41 +2328,6 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
             k_ring<<<(int)n_tasks, 64, 0, sm>>>(c.sc, S, T, (int)n_tasks, 1, S.counts, 0);
         }
         HIPCHK(hipGetLastError());
-        if (bdpt && dfilm) {
-            k_bdpt_taps<2><<<gN, BLOCK, 0, sm>>>(c.sc, S, B, BR, c.cam, N, c.tone_map, c.tone_arg, nullptr, nullptr, nullptr,
-                                                 dfilm);
-            HIPCHK(hipGetLastError());
-        } else if (bdpt && splat_lists) {
-            // this pass's taps in lumo's order: count per slot, exclusive scan (slots are tasks in
-            // order, pixels in order within a task), write, then append per task on the host
-            k_bdpt_taps<0><<<gN, BLOCK, 0, sm>>>(c.sc, S, B, BR, c.cam, N, c.tone_map, c.tone_arg, tap_cnt, nullptr, nullptr,
-                                                 nullptr);
-            uint32_t* sums = wbuf<uint32_t>(c, W_BD_SCAN, (size_t)scan_blocks(N), st);
-            if (st) return st;
-            HIPCHK(exclusive_scan(tap_cnt, tap_off, N, sums, sm));
-            k_task_tap_ranges<<<ceil_div(n_tasks + 1, BLOCK), BLOCK, 0, sm>>>(T, tap_cnt, tap_off, (int)n_tasks, N,
-                                                                              tap_ranges);
-            HIPCHK(hipMemcpyAsync(ranges_h.data(), tap_ranges, sizeof(uint64_t) * (n_tasks + 1), hipMemcpyDeviceToHost, sm));
-            HIPCHK(hipStreamSynchronize(sm));
-            const uint64_t total = ranges_h[n_tasks];
-            if (total > 0) {
-                lumo_splat* dtaps = wbuf<lumo_splat>(c, W_BD_TAPS, total, st);
-                if (st) return st;
-                k_bdpt_taps<1><<<gN, BLOCK, 0, sm>>>(c.sc, S, B, BR, c.cam, N, c.tone_map, c.tone_arg, nullptr, tap_off,
-                                                     dtaps, nullptr);
-                HIPCHK(hipGetLastError());
-                taps_h.resize(total);
-                HIPCHK(hipMemcpyAsync(taps_h.data(), dtaps, sizeof(lumo_splat) * total, hipMemcpyDeviceToHost, sm));
-                HIPCHK(hipStreamSynchronize(sm));
-                for (size_t i = 0; i < n_tasks; ++i) {
-                    const uint64_t a = ranges_h[i], b = ranges_h[i + 1];
-                    for (uint64_t k = a; k < b; ++k) {
-                        if (n_splats[i] < out[i].splat_cap) out[i].splats[n_splats[i]] = taps_h[k];
-                        n_splats[i]++;
-                    }
-                }
-            }
-        }
     }
     // results
     // Per-task {sum w*rgb, sum w} tiles: straight into the caller's buffers when they are laid out
@@ -2778,857 +2413,10 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
     return splat_oom ? LUMO_ERR_OOM : LUMO_OK;
 }
 
-// ------------------------------------------------------------------ options (LUMO_OPT_*)
-const char* const kOptEnv[LUMO_OPT_COUNT] = {
-    "LUMO_TIMING", "LUMO_LDS", "LUMO_TOP", "LUMO_FUSED", "LUMO_TAIL", "LUMO_PIPELINE", "LUMO_HEADS", "LUMO_MERGE",
-    "LUMO_DYN", "LUMO_BOUNCE_THREADS", "LUMO_SPLIT_PIPE", "LUMO_SPLIT_GROUPS", "LUMO_BDPT_TAIL", "LUMO_BOUNCE_AHEAD",
-    "LUMO_LDS_GRID", "LUMO_TOP_GRID", "LUMO_TOP_KB", "LUMO_KD_LDS", "LUMO_STACK_CLASS", "LUMO_FULL_KERNELS",
-    "LUMO_POISON", "LUMO_TAIL_PRIORITY", "LUMO_TOP_KD", "LUMO_TAIL_BOUNCES", "LUMO_FILM_FIRST",
-    "LUMO_BDPT_TOP", "LUMO_BDPT_GROUPS", "LUMO_RAY_SORT", "LUMO_ACCEL"};
-
-// A LUMO_* variable that names no option (e.g. a misspelt LUMO_TAIL_BELOW for LUMO_TAIL) would
-// otherwise be ignored without a trace: warn once per process.  LUMO_AMD_LIB and
-// LUMO_BENCH_BACKEND are read by the Python side.
-void warn_unknown_env() {
-    static bool done = false;
-    if (done) return;
-    done = true;
-    for (char** ev = environ; ev && *ev; ++ev) {
-        const char* kv = *ev;
-        if (std::strncmp(kv, "LUMO_", 5) != 0) continue;
-        const char* eq = std::strchr(kv, '=');
-        const size_t n = eq ? (size_t)(eq - kv) : std::strlen(kv);
-        bool known = false;
-        for (const char* name : kOptEnv) known = known || (std::strlen(name) == n && std::strncmp(name, kv, n) == 0);
-        for (const char* name : {"LUMO_AMD_LIB", "LUMO_BENCH_BACKEND"})
-            known = known || (std::strlen(name) == n && std::strncmp(name, kv, n) == 0);
-        if (!known) fprintf(stderr, "lumo_amd: %.*s names no option; ignored\n", (int)n, kv);
-    }
-}
-
-void opt_range(const Ctx& c, int k, int64_t& lo, int64_t& hi) {
-    lo = 0;
-    hi = 1;
-    switch (k) {
-        case LUMO_OPT_FUSED: lo = -1; break;
-        case LUMO_OPT_TAIL_BELOW: case LUMO_OPT_BDPT_TAIL: hi = (int64_t)1 << 31; break;
-        case LUMO_OPT_PIPELINE: hi = 3; break;
-        case LUMO_OPT_HEADS: hi = 64; break;
-        case LUMO_OPT_MERGE_PASSES: hi = MAX_MERGE; break;
-        case LUMO_OPT_BOUNCE_THREADS: lo = 64; hi = BLOCK; break;
-        case LUMO_OPT_SPLIT_PIPE: case LUMO_OPT_SPLIT_GROUPS: lo = 1; hi = 4; break;
-        case LUMO_OPT_BOUNCE_AHEAD: lo = 1; hi = Ctx::SNAP_RING / 4 - 1; break;
-        case LUMO_OPT_LDS_GRID: case LUMO_OPT_TOP_GRID: lo = 1; hi = 1 << 20; break;
-        case LUMO_OPT_TOP_KB: hi = (int64_t)(c.lds_cu / 1024); break;
-        case LUMO_OPT_KD_LDS: hi = 64; break;
-        case LUMO_OPT_TAIL_BOUNCES: lo = -1; hi = 16; break;
-        case LUMO_OPT_STACK_CLASS: hi = 64; break;
-        case LUMO_OPT_BDPT_GROUPS: lo = 1; hi = 4; break;
-        case LUMO_OPT_RAY_SORT: lo = -1; hi = 2; break;
-        default: break;
-    }
-}
-
-// The pipelined passes' tail stream (stream2), (re)created at normal or the device's highest
-// priority: the workgroups of its kernels are then dispatched ahead of the head streams' as CUs
-// free up.
-lumo_status make_tail_stream(Ctx& c, int high) {
-    (void)hipSetDevice(c.device);
-    if (c.stream2) {
-        (void)hipStreamSynchronize(c.stream2);
-        (void)hipStreamDestroy(c.stream2);
-        c.stream2 = nullptr;
-    }
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) greatest = least = 0;
-    if (hipStreamCreateWithPriority(&c.stream2, hipStreamNonBlocking, high ? greatest : least) != hipSuccess) {
-        last_hip_error() = hipErrorInvalidValue;
-        return LUMO_ERR_HIP;
-    }
-    return LUMO_OK;
-}
-
-lumo_status set_opt(Ctx& c, int k, int64_t v) {
-    if (k < 0 || k >= LUMO_OPT_COUNT) return LUMO_ERR_INVALID;
-    int64_t lo, hi;
-    opt_range(c, k, lo, hi);
-    if (v < lo || v > hi) return LUMO_ERR_INVALID;
-    if (k == LUMO_OPT_BOUNCE_THREADS && v != 64 && v != 128 && v != BLOCK) return LUMO_ERR_INVALID;
-    if (k == LUMO_OPT_STACK_CLASS && v != 0 &&
-        std::find(std::begin(STACK_CLASSES), std::end(STACK_CLASSES), (int)v) == std::end(STACK_CLASSES))
-        return LUMO_ERR_INVALID;
-    Opts& o = c.o;
-    const int iv = (int)v;
-    switch (k) {
-        case LUMO_OPT_TIMING: o.timing = iv; break;
-        case LUMO_OPT_LDS_STAGING: o.lds = iv; break;
-        case LUMO_OPT_TOP_STAGING: o.top = iv; break;
-        case LUMO_OPT_FUSED: o.fused = iv; break;
-        case LUMO_OPT_TAIL_BELOW: o.tail_below = (uint32_t)v; break;
-        case LUMO_OPT_PIPELINE: o.pipeline = iv; break;
-        case LUMO_OPT_HEADS: o.heads = iv; break;
-        case LUMO_OPT_MERGE_PASSES: o.merge = iv; break;
-        case LUMO_OPT_DYN_FETCH: o.dyn = iv; break;
-        case LUMO_OPT_BOUNCE_THREADS: o.bounce_threads = iv; break;
-        case LUMO_OPT_SPLIT_PIPE: o.split_pipe = iv; break;
-        case LUMO_OPT_SPLIT_GROUPS: o.split_groups = iv; break;
-        case LUMO_OPT_BDPT_TAIL: o.bdpt_tail = (uint32_t)v; break;
-        case LUMO_OPT_BOUNCE_AHEAD: o.bounce_ahead = iv; break;
-        case LUMO_OPT_LDS_GRID: o.lds_grid = iv; break;
-        case LUMO_OPT_TOP_GRID: o.top_grid = iv; break;
-        case LUMO_OPT_TOP_KB: o.top_kb = iv; break;
-        case LUMO_OPT_KD_LDS: o.kd_lds = iv; break;
-        case LUMO_OPT_STACK_CLASS: o.stack_class = iv; break;
-        case LUMO_OPT_FULL_KERNELS: o.full_kernels = iv; break;
-        case LUMO_OPT_POISON: o.poison = iv; break;
-        case LUMO_OPT_TOP_KD: o.top_kd = iv; break;
-        case LUMO_OPT_TAIL_BOUNCES: o.tail_bounces = iv; break;
-        case LUMO_OPT_FILM_FIRST: o.film_first = iv; break;
-        case LUMO_OPT_BDPT_TOP: o.bdpt_top = iv; break;
-        case LUMO_OPT_BDPT_GROUPS: o.bdpt_groups = iv; break;
-        case LUMO_OPT_RAY_SORT: o.ray_sort = iv; break;
-        case LUMO_OPT_ACCEL: o.accel = iv; break;
-        case LUMO_OPT_TAIL_PRIORITY:
-            if (iv != o.tail_priority) {
-                const lumo_status e = make_tail_stream(c, iv);
-                if (e) return e;
-            }
-            o.tail_priority = iv;
-            break;
-        default: return LUMO_ERR_INVALID;
-    }
-    return LUMO_OK;
-}
-
-int64_t get_opt(const Ctx& c, int k) {
-    const Opts& o = c.o;
-    switch (k) {
-        case LUMO_OPT_TIMING: return o.timing;
-        case LUMO_OPT_LDS_STAGING: return o.lds;
-        case LUMO_OPT_TOP_STAGING: return o.top;
-        case LUMO_OPT_FUSED: return o.fused;
-        case LUMO_OPT_TAIL_BELOW: return o.tail_below;
-        case LUMO_OPT_PIPELINE: return o.pipeline;
-        case LUMO_OPT_HEADS: return o.heads;
-        case LUMO_OPT_MERGE_PASSES: return o.merge;
-        case LUMO_OPT_DYN_FETCH: return o.dyn;
-        case LUMO_OPT_BOUNCE_THREADS: return o.bounce_threads;
-        case LUMO_OPT_SPLIT_PIPE: return o.split_pipe;
-        case LUMO_OPT_SPLIT_GROUPS: return o.split_groups;
-        case LUMO_OPT_BDPT_TAIL: return o.bdpt_tail;
-        case LUMO_OPT_BOUNCE_AHEAD: return o.bounce_ahead;
-        case LUMO_OPT_LDS_GRID: return o.lds_grid;
-        case LUMO_OPT_TOP_GRID: return o.top_grid;
-        case LUMO_OPT_TOP_KB: return o.top_kb;
-        case LUMO_OPT_KD_LDS: return o.kd_lds;
-        case LUMO_OPT_STACK_CLASS: return o.stack_class;
-        case LUMO_OPT_FULL_KERNELS: return o.full_kernels;
-        case LUMO_OPT_POISON: return o.poison;
-        case LUMO_OPT_TAIL_PRIORITY: return o.tail_priority;
-        case LUMO_OPT_TOP_KD: return o.top_kd;
-        case LUMO_OPT_TAIL_BOUNCES: return o.tail_bounces;
-        case LUMO_OPT_FILM_FIRST: return o.film_first;
-        case LUMO_OPT_BDPT_TOP: return o.bdpt_top;
-        case LUMO_OPT_BDPT_GROUPS: return o.bdpt_groups;
-        case LUMO_OPT_RAY_SORT: return o.ray_sort;
-        case LUMO_OPT_ACCEL: return o.accel;
-        default: return 0;
-    }
-}
-
 }  // namespace
 
 // ================================================================== C ABI
 extern "C" {
-
-int lumo_abi_version(void) { return LUMO_ABI_VERSION; }
-
-int lumo_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-const char* lumo_status_str(lumo_status st) {
-    switch (st) {
-        case LUMO_OK: return "ok";
-        case LUMO_ERR_INVALID: return "invalid argument";
-        case LUMO_ERR_NO_DEVICE: return "no gfx950 device";
-        case LUMO_ERR_HIP: return hipGetErrorString(last_hip_error());
-        case LUMO_ERR_NO_SCENE: return "no scene uploaded";
-        case LUMO_ERR_NO_CAMERA: return "no camera set";
-        case LUMO_ERR_UNSUPPORTED: return "unsupported";
-        case LUMO_ERR_OOM: return "out of device memory";
-        default: return "unknown";
-    }
-}
-
-lumo_status lumo_create(int device, void** ctx_out) {
-    if (!ctx_out) return LUMO_ERR_INVALID;
-    *ctx_out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return LUMO_ERR_NO_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return LUMO_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return LUMO_ERR_NO_DEVICE;
-    HIPCHK(hipSetDevice(device));
-    Ctx* c = new (std::nothrow) Ctx();
-    if (!c) return LUMO_ERR_OOM;
-    c->device = device;
-    const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    c->o.top_grid = std::max(1, cus / 2);
-    c->o.lds_grid = cus * 3 / 2;
-    if (prop.maxSharedMemoryPerMultiProcessor > 0) c->lds_cu = prop.maxSharedMemoryPerMultiProcessor;
-    if (prop.sharedMemPerBlock > 0) c->lds_block = std::min(c->lds_cu, (size_t)prop.sharedMemPerBlock);
-    c->o.top_kb = (int)(c->lds_cu / 1024);
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return LUMO_ERR_HIP;
-    }
-    if (make_tail_stream(*c, c->o.tail_priority) != LUMO_OK ||
-        hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipStreamDestroy(c->stream);
-        delete c;
-        return LUMO_ERR_HIP;
-    }
-    for (int i = 0; i < 4; ++i) {
-        (void)hipEventCreateWithFlags(&c->pass_ev[i], hipEventDisableTiming);
-        (void)hipEventCreateWithFlags(&c->tail_ev[i], hipEventDisableTiming);
-        (void)hipEventCreateWithFlags(&c->cam_ev[i], hipEventDisableTiming);
-        (void)hipEventCreateWithFlags(&c->film_ev[i], hipEventDisableTiming);
-    }
-    for (int i = 0; i < Ctx::SNAP_RING; ++i) (void)hipEventCreateWithFlags(&c->snap_ev[i], hipEventDisableTiming);
-    for (int i = 0; i < 4; ++i) (void)hipEventCreateWithFlags(&c->bd_ev[i], hipEventDisableTiming);
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->bd_totals_h), sizeof(uint32_t) * 8) != hipSuccess) {
-        (void)hipStreamDestroy(c->stream);
-        delete c;
-        return LUMO_ERR_OOM;
-    }
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->snap), sizeof(uint32_t) * CNT_N * Ctx::SNAP_RING) != hipSuccess) {
-        (void)hipStreamDestroy(c->stream);
-        delete c;
-        return LUMO_ERR_OOM;
-    }
-    if (hipMalloc(reinterpret_cast<void**>(&c->bargs), 4 * sizeof(BounceArgs)) != hipSuccess) {
-        (void)hipStreamDestroy(c->stream);
-        delete c;
-        return LUMO_ERR_OOM;
-    }
-    // the environment's overrides of the defaults: integers; the 0 / 1 switches also take
-    // on / off, true / false, yes / no.  A value that does not parse is ignored and an
-    // out-of-range one clamped, each with a one-line warning on stderr
-    for (int k = 0; k < LUMO_OPT_COUNT; ++k) {
-        const char* e = std::getenv(kOptEnv[k]);
-        if (!e || !*e) continue;
-        int64_t lo = 0, hi = 0;
-        opt_range(*c, k, lo, hi);
-        char* end = nullptr;
-        int64_t v = (int64_t)std::strtoll(e, &end, 10);
-        if (end == e || *end != '\0') {
-            auto is = [&](const char* w) { return strcasecmp(e, w) == 0; };
-            const bool sw = lo == 0 && hi == 1;
-            if (sw && (is("on") || is("true") || is("yes"))) {
-                v = 1;
-            } else if (sw && (is("off") || is("false") || is("no"))) {
-                v = 0;
-            } else {
-                fprintf(stderr, "lumo_amd: %s=%s is not a number; ignored\n", kOptEnv[k], e);
-                continue;
-            }
-        }
-        if (v < lo || v > hi) {
-            const int64_t cl = std::min(hi, std::max(lo, v));
-            fprintf(stderr, "lumo_amd: %s=%s outside [%lld, %lld]; using %lld\n", kOptEnv[k], e, (long long)lo,
-                    (long long)hi, (long long)cl);
-            v = cl;
-        }
-        if (set_opt(*c, k, v) != LUMO_OK)
-            fprintf(stderr, "lumo_amd: %s=%s not accepted; default kept\n", kOptEnv[k], e);
-    }
-    warn_unknown_env();
-    *ctx_out = c;
-    return LUMO_OK;
-}
-
-void lumo_destroy(void* ctx) {
-    Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->stream2);
-    (void)hipStreamSynchronize(c->stream3);
-    (void)hipStreamSynchronize(c->stream4);
-    free_scene(*c);
-    for (DevBuf& b : c->work)
-        if (b.p) (void)hipFree(b.p);
-    for (DevBuf& b : c->gwork)
-        if (b.p) (void)hipFree(b.p);
-    for (int i = 0; i < Ctx::SNAP_RING; ++i) (void)hipEventDestroy(c->snap_ev[i]);
-    if (c->snap) (void)hipHostFree(c->snap);
-    if (c->bargs) (void)hipFree(c->bargs);
-    if (c->bd_totals_h) (void)hipHostFree(c->bd_totals_h);
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(c->bd_ev[i]);
-    for (int i = 0; i < 4; ++i) {
-        (void)hipEventDestroy(c->pass_ev[i]);
-        (void)hipEventDestroy(c->tail_ev[i]);
-        (void)hipEventDestroy(c->cam_ev[i]);
-        (void)hipEventDestroy(c->film_ev[i]);
-    }
-    (void)hipStreamDestroy(c->stream4);
-    (void)hipStreamDestroy(c->stream3);
-    (void)hipStreamDestroy(c->stream2);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
-lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
-    Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c || !d) return LUMO_ERR_INVALID;
-    if (d->num_lights <= 0 || d->num_light_nodes <= 0 || d->num_dense_spectra < 3 || !d->materials) return LUMO_ERR_INVALID;
-    for (int i = 0; i < d->num_materials; ++i) {
-        const lumo_material& m = d->materials[i];
-        if (m.kind < LUMO_MAT_BLANK || m.kind > LUMO_MAT_MF_DIELECTRIC) return LUMO_ERR_UNSUPPORTED;
-        if (m.kind >= LUMO_MAT_MF_DIFFUSE &&
-            (m.eta_idx < 0 || m.eta_idx >= d->num_dense_spectra || m.k_idx < 0 || m.k_idx >= d->num_dense_spectra ||
-             !(m.roughness > 0.0 && m.roughness <= 1.0)))
-            return LUMO_ERR_INVALID;
-        if (m.kind == LUMO_MAT_LIGHT && (m.illuminant < 0 || m.illuminant >= d->num_dense_spectra))
-            return LUMO_ERR_INVALID;
-        for (int t : {m.albedo_tex, m.ks_tex, m.tf_tex})
-            if (t < -1 || t >= d->num_textures) return LUMO_ERR_INVALID;
-        if (m.normal_map < -1 || m.normal_map >= d->num_normal_maps) return LUMO_ERR_INVALID;
-    }
-    // texture tables (texture.rs): checkerboard children precede their parent, so sampling ends
-    for (int i = 0; i < d->num_textures; ++i) {
-        const lumo_texture& t = d->textures[i];
-        const bool ok = t.kind == LUMO_TEX_SOLID || t.kind == LUMO_TEX_MANDELBROT ||
-                        (t.kind == LUMO_TEX_IMAGE && t.width > 0 && t.height > 0 && t.first >= 0 &&
-                         (int64_t)t.first + (int64_t)t.width * t.height <= d->num_texels) ||
-                        (t.kind == LUMO_TEX_CHECKERBOARD && t.first >= 0 && t.first < i && t.second >= 0 && t.second < i) ||
-                        (t.kind == LUMO_TEX_MARBLE && t.first >= 0 && t.first < d->num_perlin);
-        if (!ok) return LUMO_ERR_INVALID;
-    }
-    for (int i = 0; i < d->num_normal_maps; ++i) {
-        const lumo_normal_map& n = d->normal_maps[i];
-        if (!(n.width > 0 && n.height > 0 && n.first >= 0 &&
-              (int64_t)n.first + (int64_t)n.width * n.height <= d->num_normal_texels))
-            return LUMO_ERR_INVALID;
-    }
-    for (int i = 0; i < d->num_lights + d->num_objects; ++i) {
-        const lumo_object& o = i < d->num_lights ? d->lights[i] : d->objects[i - d->num_lights];
-        if (o.type < LUMO_OBJ_KDMESH || o.type > LUMO_OBJ_SPHERE) return LUMO_ERR_UNSUPPORTED;
-        if (o.type == LUMO_OBJ_SPHERE && !(o.radius != 0.0 && o.area > 0.0)) return LUMO_ERR_INVALID;
-        if (o.xform >= d->num_transforms || (o.xform >= 0 && !d->transforms)) return LUMO_ERR_INVALID;
-        if (o.type == LUMO_OBJ_TRIANGLE && (o.tri_base < 0 || o.tri_base >= d->num_triangles)) return LUMO_ERR_INVALID;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    free_scene(*c);
-    DScene& s = c->sc;
-    lumo_status st = LUMO_OK;
-    auto chk = [&](lumo_status x) {
-        if (x && !st) st = x;
-    };
-    chk(upload(*c, d->vertices, (size_t)3 * d->num_vertices, &s.vertices));
-    c->sort_lo = V3{0.0, 0.0, 0.0};  // no world box: every origin in cell 0 (the octant still sorts)
-    c->sort_scale = V3{0.0, 0.0, 0.0};
-    if (d->num_object_nodes > 0 && d->object_nodes) {  // ray sorting's cells: the objects BVH's world box
-        const lumo_bvh_node& r = d->object_nodes[0];
-        double lo[3], sc3[3];
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = r.bmin[a];
-            const double ext = r.bmax[a] - r.bmin[a];
-            sc3[a] = ext > 0.0 && std::isfinite(ext) ? 8.0 / ext : 0.0;  // 8 cells per axis (scan.h rs_key)
-        }
-        c->sort_lo = V3{lo[0], lo[1], lo[2]};
-        c->sort_scale = V3{sc3[0], sc3[1], sc3[2]};
-    }
-    chk(upload(*c, d->normals, (size_t)3 * d->num_normals, &s.normals));
-    chk(upload(*c, d->uvs, (size_t)2 * d->num_uvs, &s.uvs));
-    chk(upload(*c, d->triangles, (size_t)d->num_triangles, &s.tris));
-    chk(upload(*c, d->kd_nodes, (size_t)d->num_kd_nodes, &s.kd));
-    chk(upload(*c, d->kd_items, (size_t)d->num_kd_items, &s.kd_items));
-    // device BVHs (DBvh, dscene.h): right child -> escape index (lumo's preorder successor of the
-    // subtree), left child explicit, nodes stored breadth-first so the top levels are a prefix
-    bool bvh_ok = true;
-    auto escapes = [&](const lumo_bvh_node* nodes, int n, std::vector<DBvh>& out) {
-        out.assign(n > 0 ? n : 0, DBvh{});
-        if (n <= 0) return;
-        std::vector<int32_t> esc(n, -1);
-        for (int i = 0; i < n; ++i) {  // parents precede children (preorder)
-            const lumo_bvh_node& b = nodes[i];
-            if (b.count == 0) {
-                if (i + 1 >= n || (b.right >= n)) {
-                    bvh_ok = false;
-                    return;
-                }
-                esc[i + 1] = b.right >= 0 ? b.right : esc[i];
-                if (b.right >= 0) esc[b.right] = esc[i];
-            }
-        }
-        std::vector<int32_t> order, at(n, -1);  // breadth-first order; at[old] = new index
-        order.reserve(n);
-        order.push_back(0);
-        at[0] = 0;
-        for (size_t h = 0; h < order.size(); ++h) {
-            const int i = order[h];
-            if (nodes[i].count != 0) continue;
-            for (const int ch : {i + 1, nodes[i].right}) {
-                if (ch < 0) continue;
-                if (at[ch] >= 0) {  // not a tree
-                    bvh_ok = false;
-                    return;
-                }
-                at[ch] = (int32_t)order.size();
-                order.push_back(ch);
-            }
-        }
-        if ((int)order.size() != n) {  // unreachable nodes: not lumo's layout
-            bvh_ok = false;
-            return;
-        }
-        for (int k = 0; k < n; ++k) {
-            const int i = order[k];
-            DBvh& o = out[k];
-            for (int a = 0; a < 3; ++a) {
-                o.bmin[a] = nodes[i].bmin[a];
-                o.bmax[a] = nodes[i].bmax[a];
-            }
-            o.escape = esc[i] >= 0 ? at[esc[i]] : -1;
-            o.left = nodes[i].count == 0 ? at[i + 1] : -1;
-            o.first = nodes[i].first;
-            o.count = nodes[i].count;
-        }
-    };
-    std::vector<DBvh> obvh, lbvh;
-    escapes(d->object_nodes, d->num_object_nodes, obvh);
-    escapes(d->light_nodes, d->num_light_nodes, lbvh);
-    if (!bvh_ok) {
-        free_scene(*c);
-        return LUMO_ERR_INVALID;
-    }
-    chk(upload(*c, obvh.data(), obvh.size(), &s.onodes));
-    chk(upload(*c, d->object_items, (size_t)d->num_object_items, &s.oitems));
-    chk(upload(*c, lbvh.data(), lbvh.size(), &s.lnodes));
-    chk(upload(*c, d->light_items, (size_t)d->num_light_items, &s.litems));
-    chk(upload(*c, d->alias_prob, (size_t)d->num_lights, &s.alias_prob));
-    chk(upload(*c, d->alias_idx, (size_t)d->num_lights, &s.alias_idx));
-    chk(upload(*c, d->alias_pdf, (size_t)d->num_lights, &s.alias_pdf));
-    chk(upload(*c, d->materials, (size_t)d->num_materials, &s.mats));
-    chk(upload(*c, d->dense_spectra, (size_t)95 * d->num_dense_spectra, &s.dense));
-    chk(upload(*c, d->transforms, (size_t)d->num_transforms, &s.xforms));
-    chk(upload(*c, d->textures, (size_t)d->num_textures, &s.textures));
-    chk(upload(*c, d->texels, (size_t)d->num_texels, &s.texels));
-    chk(upload(*c, d->normal_maps, (size_t)d->num_normal_maps, &s.nmaps));
-    chk(upload(*c, d->normal_texels, (size_t)3 * d->num_normal_texels, &s.ntexels));
-    chk(upload(*c, d->perlin, (size_t)d->num_perlin, &s.perlin));
-    // device-only layouts: triangle vertex soup and 16-B kd nodes
-    std::vector<double> tv((size_t)TV_STRIDE * d->num_triangles, 0.0);
-    for (int i = 0; i < d->num_triangles; ++i)
-        for (int k = 0; k < 3; ++k)
-            for (int a = 0; a < 3; ++a) tv[(size_t)TV_STRIDE * i + 3 * k + a] = d->vertices[3 * d->triangles[i].v[k] + a];
-    // kd trees in cache-line treelets: each tree (from each distinct kd_root) is cut into groups of
-    // up to 8 nodes (128 B) taken breadth-first from a group root, so a node's children and
-    // grandchildren are usually in the line the node itself came in; trees under 8 nodes are
-    // packed without alignment.  Children are stored as explicit indices (DKd::left).
-    std::vector<int32_t> kd_new(d->num_kd_nodes, -1);
-    std::vector<DKd> kdp;
-    std::vector<std::pair<size_t, size_t>> kd_trees;  // [first, end) of each tree's treelets in kdp
-    {
-        std::vector<int32_t> order;  // old indices in new order (-1: padding)
-        auto kid = [&](int i, int which) { return which == 0 ? i + 1 : d->kd_nodes[i].right; };
-        auto valid = [&](int i) { return i >= 0 && i < d->num_kd_nodes; };
-        auto place_tree = [&](int root) {
-            if (!valid(root) || kd_new[root] >= 0) return;
-            struct Extent {
-                std::vector<std::pair<size_t, size_t>>& v;
-                std::vector<int32_t>& o;
-                size_t lo;
-                ~Extent() { v.emplace_back(lo, o.size()); }
-            } extent{kd_trees, order, order.size()};
-            int size = 0;  // nodes of the tree (bounded walk)
-            {
-                std::vector<int32_t> st{root};
-                while (!st.empty() && size <= 8) {
-                    const int i = st.back();
-                    st.pop_back();
-                    size++;
-                    if (!d->kd_nodes[i].leaf) {
-                        for (int w = 0; w < 2; ++w)
-                            if (valid(kid(i, w))) st.push_back(kid(i, w));
-                    }
-                }
-            }
-            std::deque<int32_t> groups{root};
-            while (!groups.empty()) {
-                const int g = groups.front();
-                groups.pop_front();
-                if (size > 8)
-                    while (order.size() % 8) order.push_back(-1);  // start a 128-B line
-                std::deque<int32_t> bfs{g};
-                int used = 0;
-                while (!bfs.empty()) {
-                    const int i = bfs.front();
-                    bfs.pop_front();
-                    if (used == 8) {
-                        groups.push_back(i);
-                        continue;
-                    }
-                    kd_new[i] = (int32_t)order.size();
-                    order.push_back(i);
-                    used++;
-                    if (!d->kd_nodes[i].leaf)
-                        for (int w = 0; w < 2; ++w)
-                            if (valid(kid(i, w)) && kd_new[kid(i, w)] < 0) bfs.push_back(kid(i, w));
-                }
-            }
-        };
-        for (int i = 0; i < d->num_objects; ++i)
-            if (d->objects[i].type == LUMO_OBJ_KDMESH || d->objects[i].type == LUMO_OBJ_RECTANGLE) place_tree(d->objects[i].kd_root);
-        for (int i = 0; i < d->num_lights; ++i)
-            if (d->lights[i].type == LUMO_OBJ_KDMESH || d->lights[i].type == LUMO_OBJ_RECTANGLE) place_tree(d->lights[i].kd_root);
-        kdp.assign(order.size(), DKd{});
-        for (size_t j = 0; j < order.size(); ++j) {
-            const int i = order[j];
-            if (i < 0) continue;
-            const lumo_kd_node& n = d->kd_nodes[i];
-            DKd k{};
-            if (n.leaf) {
-                k.u.leaf.first = n.first;
-                k.u.leaf.count = n.count;
-                k.meta = 3;
-                k.left = -1;
-            } else {
-                if (!valid(n.right) || !valid(i + 1) || n.axis < 0 || n.axis > 2 || kd_new[n.right] >= (1 << 29))
-                    chk(LUMO_ERR_INVALID);
-                k.u.point = n.point;
-                k.meta = (kd_new[n.right] << 2) | n.axis;
-                k.left = kd_new[i + 1];
-            }
-            kdp[j] = k;
-        }
-    }
-    auto relaid = [&](const lumo_object* src, int n) {  // objects / lights with their new kd roots
-        std::vector<lumo_object> v(src, src + n);
-        for (lumo_object& o : v)
-            if ((o.type == LUMO_OBJ_KDMESH || o.type == LUMO_OBJ_RECTANGLE) && o.kd_root >= 0 &&
-                o.kd_root < d->num_kd_nodes)
-                o.kd_root = kd_new[o.kd_root];
-        return v;
-    };
-    const std::vector<lumo_object> objs_dev = relaid(d->objects, d->num_objects);
-    const std::vector<lumo_object> lights_dev = relaid(d->lights, d->num_lights);
-    auto trav_view = [](const std::vector<lumo_object>& v) {  // DObj (dscene.h): what the walks read
-        std::vector<DObj> t(v.size());
-        for (size_t i = 0; i < v.size(); ++i) {
-            const lumo_object& o = v[i];
-            DObj& x = t[i];
-            for (int a = 0; a < 3; ++a) {
-                x.bmin[a] = o.bmin[a];
-                x.bmax[a] = o.bmax[a];
-            }
-            if (o.type == LUMO_OBJ_SPHERE) x.bmin[0] = o.radius;
-            x.kd_root = o.kd_root;
-            x.tri_base = o.tri_base;
-            x.item_base = o.item_base;
-            x.tx = ((o.xform + 1) << 2) | o.type;
-        }
-        return t;
-    };
-    const std::vector<DObj> tobjs = trav_view(objs_dev), tlights = trav_view(lights_dev);
-    chk(upload(*c, objs_dev.data(), objs_dev.size(), &s.objs));
-    chk(upload(*c, lights_dev.data(), lights_dev.size(), &s.lights));
-    chk(upload(*c, tobjs.data(), tobjs.size(), &s.tobjs));
-    chk(upload(*c, tlights.data(), tlights.size(), &s.tlights));
-    chk(upload(*c, tv.data(), tv.size(), &s.tv));
-    chk(upload(*c, kdp.data(), kdp.size(), &s.kdp));
-    // wide accel (LUMO_OPT_ACCEL = 1, wbvh.h): built from the scene description.  The sampled light's
-    // own hit keeps lumo's kd walk with a WL_STK-entry stack, so every light's kd tree must fit it;
-    // a scene the build refuses keeps lumo's structures (lumo_scene_info.accel = 0).
-    wbvh::Accel acc;
-    s.accel = 0;
-    s.w_oroot = s.w_lroot = wbvh::NONE;
-    s.wnodes = s.wnodes_lds = nullptr;
-    s.wtv = nullptr;
-    s.w_oblas = s.w_lblas = nullptr;
-    s.wn_lds = s.top_wnodes = 0;
-    s.w_maxabs = 0.0;
-    s.off_top_wnodes = 0;
-    s.off_wnodes = s.off_wtv = s.off_woblas = s.off_wlblas = 0;
-    c->w_nodes = c->w_tris = c->w_stack = c->w_depth = 0;
-    if (c->o.accel && !st) {
-        acc = wbvh::build_accel(*d);  // refuses light kd trees deeper than WL_STK
-        if (acc.ok) {
-            s.accel = 1;
-            s.w_oroot = acc.obj_root;
-            s.w_lroot = acc.light_root;
-            s.w_maxabs = (double)acc.max_abs;
-            chk(upload(*c, acc.nodes.data(), acc.nodes.size(), &s.wnodes));
-            chk(upload(*c, acc.tv.data(), acc.tv.size(), &s.wtv));
-            chk(upload(*c, acc.obj_blas.data(), acc.obj_blas.size(), &s.w_oblas));
-            chk(upload(*c, acc.light_blas.data(), acc.light_blas.size(), &s.w_lblas));
-            c->w_nodes = (int)acc.nodes.size();
-            c->w_tris = (int)(acc.tv.size() / wbvh::TV);
-            c->w_stack = acc.max_stack;
-            c->w_depth = acc.depth;
-        } else {
-            fprintf(stderr, "lumo_amd: the wide accel refused this scene (a light kd tree deeper than %d or a "
-                    "walk stack of %d); walking lumo's structures\n", WL_STK, acc.max_stack);
-        }
-    }
-    if (st) {
-        free_scene(*c);
-        return st;
-    }
-    s.n_onodes = d->num_object_nodes;
-    s.n_lnodes = d->num_light_nodes;
-    s.n_lights = d->num_lights;
-    s.n_objs = d->num_objects;
-    {   // packed traversal set for LDS staging (scenes up to 48 KiB)
-        std::vector<char> hot;
-        auto put = [&](const void* p, size_t bytes) -> uint32_t {
-            const size_t off = (hot.size() + 15) & ~(size_t)15;
-            hot.resize(off + ((bytes + 15) & ~(size_t)15), 0);
-            if (bytes) std::memcpy(hot.data() + off, p, bytes);
-            return (uint32_t)off;
-        };
-        s.off_onodes = put(obvh.data(), sizeof(DBvh) * obvh.size());
-        s.off_oitems = put(d->object_items, sizeof(int32_t) * d->num_object_items);
-        s.off_lnodes = put(lbvh.data(), sizeof(DBvh) * lbvh.size());
-        s.off_litems = put(d->light_items, sizeof(int32_t) * d->num_light_items);
-        s.off_objs = put(objs_dev.data(), sizeof(lumo_object) * objs_dev.size());
-        s.off_lights = put(lights_dev.data(), sizeof(lumo_object) * lights_dev.size());
-        s.off_kdp = put(kdp.data(), sizeof(DKd) * kdp.size());
-        s.off_kd_items = put(d->kd_items, sizeof(int32_t) * d->num_kd_items);
-        s.off_tris = put(d->triangles, sizeof(lumo_triangle) * d->num_triangles);
-        s.off_tv = put(tv.data(), sizeof(double) * tv.size());
-        s.off_xforms = put(d->transforms, sizeof(lumo_transform) * d->num_transforms);
-        s.off_tobjs = put(tobjs.data(), sizeof(DObj) * tobjs.size());
-        s.off_tlights = put(tlights.data(), sizeof(DObj) * tlights.size());
-        if (s.accel) {
-            s.off_wnodes = put(acc.nodes.data(), sizeof(wbvh::Node) * acc.nodes.size());
-            s.off_wtv = put(acc.tv.data(), sizeof(double) * acc.tv.size());
-            s.off_woblas = put(acc.obj_blas.data(), sizeof(int32_t) * acc.obj_blas.size());
-            s.off_wlblas = put(acc.light_blas.data(), sizeof(int32_t) * acc.light_blas.size());
-        }
-        s.hot_bytes = 0;
-        if (hot.size() <= 48 * 1024) {
-            const char* dp = nullptr;
-            chk(upload(*c, hot.data(), hot.size(), &dp));
-            if (st) {
-                free_scene(*c);
-                return st;
-            }
-            s.hot = dp;
-            s.hot_bytes = (uint32_t)hot.size();
-        }
-    }
-    {   // TOP set for larger scenes (DScene::top): the object items and traversal records, the
-        // objects BVH and as much of the lights BVH as fits, both breadth-first prefixes
-        s.top = nullptr;
-        s.top_bytes = 0;
-        s.top_onodes = s.top_lnodes = 0;
-        s.onodes_lds = s.lnodes_lds = nullptr;
-        s.n_onodes_lds = s.n_lnodes_lds = 0;
-        const size_t cap = std::min((size_t)c->o.top_kb * 1024, c->lds_cu);
-        const size_t budget = cap > 256 ? cap - 256 : 0;  // 256 B: the kernels' static LDS
-        const size_t objs_b = ((sizeof(int32_t) * d->num_object_items + 15) & ~(size_t)15) + sizeof(DObj) * tobjs.size();
-        const size_t wobjs_b = ((sizeof(DObj) * tobjs.size() + 15) & ~(size_t)15);
-        if (s.accel && s.hot_bytes == 0 && budget >= 4096 && wobjs_b + 16 * sizeof(wbvh::Node) <= budget) {
-            // wide accel: the object records (object leaves) and a breadth-first prefix of the nodes
-            // (the top levels of every tree, wbvh_build.h); no kd stack or treelets (the light's own
-            // kd walk reads HBM)
-            std::vector<char> top;
-            auto put = [&](const void* p, size_t bytes) -> uint32_t {
-                const size_t off = (top.size() + 15) & ~(size_t)15;
-                top.resize(off + ((bytes + 15) & ~(size_t)15), 0);
-                if (bytes) std::memcpy(top.data() + off, p, bytes);
-                return (uint32_t)off;
-            };
-            s.off_top_oitems = 0;
-            s.off_top_tobjs = put(tobjs.data(), sizeof(DObj) * tobjs.size());
-            const size_t left = budget - top.size();
-            const size_t nw = std::min(acc.nodes.size(), left / sizeof(wbvh::Node));
-            s.off_top_wnodes = put(acc.nodes.data(), sizeof(wbvh::Node) * nw);
-            s.top_wnodes = (int32_t)nw;
-            s.top_onodes = s.top_lnodes = 0;
-            s.off_top_onodes = s.off_top_lnodes = 0;
-            s.kst_cfg = 0;
-            s.top_kd_lo = s.top_kd_n = 0;
-            s.off_top_kd = 0;
-            const char* dp = nullptr;
-            chk(upload(*c, top.data(), top.size(), &dp));
-            if (st) {
-                free_scene(*c);
-                return st;
-            }
-            s.top = dp;
-            s.top_bytes = (uint32_t)top.size();
-        } else if (!s.accel && s.hot_bytes == 0 && budget >= 4096 && objs_b + 64 * sizeof(DBvh) <= budget) {
-            std::vector<char> top;
-            auto put = [&](const void* p, size_t bytes) -> uint32_t {
-                const size_t off = (top.size() + 15) & ~(size_t)15;
-                top.resize(off + ((bytes + 15) & ~(size_t)15), 0);
-                if (bytes) std::memcpy(top.data() + off, p, bytes);
-                return (uint32_t)off;
-            };
-            s.off_top_oitems = put(d->object_items, sizeof(int32_t) * d->num_object_items);
-            s.off_top_tobjs = put(tobjs.data(), sizeof(DObj) * tobjs.size());
-            size_t left = budget - top.size();
-            const size_t no = std::min(obvh.size(), left / sizeof(DBvh));
-            s.off_top_onodes = put(obvh.data(), sizeof(DBvh) * no);
-            left = budget - top.size();
-            const size_t nl = std::min(lbvh.size(), left / sizeof(DBvh));
-            s.off_top_lnodes = put(lbvh.data(), sizeof(DBvh) * nl);
-            s.top_onodes = (int32_t)no;
-            s.top_lnodes = (int32_t)nl;
-            // kd stack entries per thread in LDS after the TOP set (TOP_BLOCK threads, 12 B each),
-            // within the same budget (LUMO_OPT_TOP_KB caps the TOP kernels' whole LDS use)
-            const size_t aligned = (top.size() + 15) & ~(size_t)15;
-            const size_t lim = std::min(cap, c->lds_block);
-            size_t room = lim > aligned + 256 ? lim - aligned - 256 : 0;
-            s.kst_cfg = c->o.kd_lds > 0 ? (int32_t)std::min<size_t>((size_t)c->o.kd_lds, room / (12 * (size_t)TOP_BLOCK)) : 0;
-            room -= 12 * (size_t)TOP_BLOCK * s.kst_cfg;
-            // then, in what is left, the first treelets of the largest kd tree (its top levels: the
-            // trees are laid out breadth-first by 128-B treelet, so they are a prefix of its range)
-            s.top_kd_lo = s.top_kd_n = 0;
-            s.off_top_kd = 0;
-            size_t big = 0, big_lo = 0;
-            for (const auto& tr : kd_trees)
-                if (tr.second - tr.first > big) {
-                    big = tr.second - tr.first;
-                    big_lo = tr.first;
-                }
-            if (c->o.top_kd && big > 8 && room >= 16 * 64 + 16) {
-                const size_t nk = std::min(big, (room - 16) / sizeof(DKd));
-                s.off_top_kd = put(kdp.data() + big_lo, sizeof(DKd) * nk);
-                s.top_kd_lo = (int32_t)big_lo;
-                s.top_kd_n = (int32_t)nk;
-            }
-            const char* dp = nullptr;
-            chk(upload(*c, top.data(), top.size(), &dp));
-            if (st) {
-                free_scene(*c);
-                return st;
-            }
-            s.top = dp;
-            s.top_bytes = (uint32_t)top.size();
-        } else {
-            s.kst_cfg = 0;
-            s.top_kd_lo = s.top_kd_n = 0;
-            s.off_top_kd = 0;
-        }
-        s.kst_n = 0;
-        s.top_shm = ((s.top_bytes + 15u) & ~15u) + (uint32_t)(12 * (size_t)TOP_BLOCK * s.kst_cfg);
-    }
-    int n = d->num_lights, lg = 0;
-    while (n > 1) {
-        n >>= 1;
-        lg++;
-    }
-    s.n_shadow = lg > 1 ? lg : 1;  // scene.rs:90-92
-    // deepest pending-stack use: BVH (right children pending on a root-leaf path) and kd trees
-    auto bvh_need = [&](const lumo_bvh_node* nodes, int n) {
-        std::vector<int> pend(n > 0 ? n : 1, 0);
-        int mx = 0;
-        for (int i = 0; i < n; ++i) {  // parents precede children in lumo's layout
-            if (nodes[i].count == 0) {
-                const int p = pend[i] + (nodes[i].right >= 0 ? 1 : 0);
-                if (i + 1 < n) pend[i + 1] = std::max(pend[i + 1], p);
-                if (nodes[i].right >= 0 && nodes[i].right < n) pend[nodes[i].right] = std::max(pend[nodes[i].right], pend[i]);
-                mx = std::max(mx, p);
-            }
-        }
-        return mx;
-    };
-    const int need_b = std::max({1, bvh_need(d->object_nodes, d->num_object_nodes),
-                                 bvh_need(d->light_nodes, d->num_light_nodes)});
-    int need_k = 1;
-    {
-        std::vector<int> depth(d->num_kd_nodes > 0 ? d->num_kd_nodes : 1, 0);
-        for (int i = 0; i < d->num_kd_nodes; ++i) {
-            if (!d->kd_nodes[i].leaf) {
-                if (i + 1 < d->num_kd_nodes) depth[i + 1] = std::max(depth[i + 1], depth[i] + 1);
-                const int r = d->kd_nodes[i].right;
-                if (r >= 0 && r < d->num_kd_nodes) depth[r] = std::max(depth[r], depth[i] + 1);
-                need_k = std::max(need_k, depth[i] + 1);
-            }
-        }
-    }
-    if (need_b > 64 || need_k > 64) {
-        free_scene(*c);
-        return LUMO_ERR_UNSUPPORTED;  // lumo's fixed [_; 64] stacks would overflow too
-    }
-    auto fits = [&](int cls) { return cls >= need_k; };
-    s.stack_class = 64;
-    for (int cls : STACK_CLASSES)
-        if (fits(cls)) {
-            s.stack_class = cls;
-            break;
-        }
-    if (c->o.stack_class > 0 && fits(c->o.stack_class)) s.stack_class = c->o.stack_class;  // A/B override
-    if (s.accel) s.stack_class = 0;  // the wide walks (by_stack_class)
-    // feature class: the lean kernels cover kd meshes / rectangles with Lambertian + Light only
-    bool full = d->num_transforms > 0;
-    for (int i = 0; i < d->num_materials; ++i)
-        full = full || (d->materials[i].kind != LUMO_MAT_LAMBERTIAN && d->materials[i].kind != LUMO_MAT_LIGHT &&
-                        d->materials[i].kind != LUMO_MAT_BLANK);
-    for (int i = 0; i < d->num_objects; ++i)
-        full = full || (d->objects[i].type != LUMO_OBJ_KDMESH && d->objects[i].type != LUMO_OBJ_RECTANGLE);
-    for (int i = 0; i < d->num_lights; ++i) full = full || d->lights[i].type != LUMO_OBJ_RECTANGLE;
-    bool textured = false;  // textures and bump maps: feature class 2 (the only kernels that sample them)
-    for (int i = 0; i < d->num_materials; ++i) {
-        const lumo_material& m = d->materials[i];
-        textured = textured || m.albedo_tex >= 0 || m.ks_tex >= 0 || m.tf_tex >= 0 || m.normal_map >= 0;
-    }
-    full = full || c->o.full_kernels != 0;  // A/B switch
-    s.full = textured ? 2 : (full ? 1 : 0);
-    c->has_scene = true;
-    return LUMO_OK;
-}
-
-lumo_status lumo_camera_set(void* ctx, const lumo_camera_desc* d) {
-    Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c || !d) return LUMO_ERR_INVALID;
-    if (d->orthographic != 0 && d->orthographic != 1) return LUMO_ERR_INVALID;
-    if (d->width <= 0 || d->height <= 0 || !(d->filter_radius > 0.0) || !(d->filter_sigma > 0.0)) return LUMO_ERR_INVALID;
-    auto get = [](const double (&a)[2][16]) {
-        Xform x;
-        M4* ms[2] = {&x.m, &x.inv};
-        for (int q = 0; q < 2; ++q) {
-            V4* rows[4] = {&ms[q]->y0, &ms[q]->y1, &ms[q]->y2, &ms[q]->y3};
-            for (int r = 0; r < 4; ++r) *rows[r] = V4{a[q][4 * r], a[q][4 * r + 1], a[q][4 * r + 2], a[q][4 * r + 3]};
-        }
-        return x;
-    };
-    auto m3 = [](const double* a) { return M3{V3{a[0], a[1], a[2]}, V3{a[3], a[4], a[5]}, V3{a[6], a[7], a[8]}}; };
-    c->cam.wtc = get(d->world_to_camera);
-    c->cam.sctr = get(d->screen_to_raster);
-    c->cam.cts = get(d->camera_to_screen);
-    c->cam.lens_radius = d->lens_radius;
-    c->cam.focal_length = d->focal_length;
-    c->cam.wb = m3(d->white_balance);
-    c->cam.x2r = m3(d->xyz_to_rgb);
-    c->cam.fr = d->filter_radius;
-    c->cam.fsig = d->filter_sigma;
-    c->cam.width = (double)d->width;
-    c->cam.height = (double)d->height;
-    c->cam.orthographic = d->orthographic;
-    {   // CameraConfig::new (camera.rs:47-76): image plane area at z = 1
-        const DCam& k = c->cam;
-        V3 p_min3 = xf_pt_inv(k.sctr, V3{0.0, 0.0, 0.0});
-        V3 p_max3 = xf_pt_inv(k.sctr, V3{k.width, k.height, 0.0});
-        p_min3 = xf_pt_inv(k.cts, p_min3);
-        p_max3 = xf_pt_inv(k.cts, p_max3);
-        const V2 p_min = V2{p_min3.x, p_min3.y} / (p_min3.z == 0.0 ? 1.0 : p_min3.z);
-        const V2 p_max = V2{p_max3.x, p_max3.y} / (p_max3.z == 0.0 ? 1.0 : p_max3.z);
-        const V2 pd = p_max - p_min;
-        c->cam.image_plane_area = fabs(pd.x * pd.y);
-    }
-    if ((uint64_t)std::ceil(d->filter_radius - 0.5) != 1) return LUMO_ERR_UNSUPPORTED;  // 3x3 gather footprint
-    c->has_camera = true;
-    return LUMO_OK;
-}
 
 lumo_status lumo_render_tiles(void* ctx, const lumo_tile_task* tasks, size_t n, const lumo_render_cfg* cfg,
                               lumo_tile_result* out) {
@@ -3699,13 +2487,13 @@ lumo_status lumo_trace(void* ctx, const lumo_ray_soa* rays, size_t n, lumo_hit_s
     int32_t* prim = wbuf<int32_t>(*c, W_HIT_TRI, n, st);
     unsigned long long* tc = wbuf<unsigned long long>(*c, W_TCOUNT, TC_ALL + TC_STATS, st);
     if (st) return st;
-    hipStream_t sm = c->stream;
+    hipStream_t sm = c->streams[0];
     HIPCHK(hipMemcpyAsync(o, rays->origin, sizeof(double) * 3 * n, hipMemcpyHostToDevice, sm));
     HIPCHK(hipMemcpyAsync(d, rays->dir, sizeof(double) * 3 * n, hipMemcpyHostToDevice, sm));
     if (any_hit) HIPCHK(hipMemcpyAsync(light, rays->light, sizeof(int32_t) * n, hipMemcpyHostToDevice, sm));
     HIPCHK(hipMemsetAsync(tc, 0, sizeof(unsigned long long) * (TC_ALL + TC_STATS), sm));
     const bool top = c->o.top && c->sc.top_bytes > 0 && !(c->o.lds && c->sc.hot_bytes > 0);
-    const int grid = top ? std::min(ceil_div(n, TOP_BLOCK), c->o.top_grid) : ceil_div(n, BLOCK);
+    const int grid = top ? std::min(ceil_div(n, TOP_BLOCK), (int)c->o.top_grid) : ceil_div(n, BLOCK);
     by_stack_class(c->sc.stack_class, [&](auto K) {
         launch_trace<decltype(K)::value>(grid, sm, c->sc, o, d, light, (int)n, any_hit, t, kind, obj, prim, tc, top);
     });
@@ -3725,29 +2513,6 @@ lumo_status lumo_trace(void* ctx, const lumo_ray_soa* rays, size_t n, lumo_hit_s
     return LUMO_OK;
 }
 
-lumo_status lumo_scene_info(void* ctx, lumo_scene_info_t* info) {
-    Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c || !info) return LUMO_ERR_INVALID;
-    if (!c->has_scene) return LUMO_ERR_NO_SCENE;
-    info->stack_class = c->sc.stack_class;
-    info->lds_bytes = c->o.lds ? (int32_t)c->sc.hot_bytes : 0;
-    info->full_kernels = c->sc.full;
-    info->n_shadow = c->sc.n_shadow;
-    const bool top = c->o.top && c->sc.top_bytes > 0 && !(c->o.lds && c->sc.hot_bytes > 0);
-    info->top_bytes = top ? (int32_t)c->sc.top_bytes : 0;
-    info->top_object_nodes = c->sc.top_onodes;
-    info->top_light_nodes = c->sc.top_lnodes;
-    info->top_kd_nodes = top ? c->sc.top_kd_n : 0;
-    info->top_shm = top ? (int32_t)c->sc.top_shm : 0;
-    info->accel = c->sc.accel;
-    info->wide_nodes = c->w_nodes;
-    info->wide_tris = c->w_tris;
-    info->wide_stack = c->w_stack;
-    info->wide_depth = c->w_depth;
-    info->top_wide_nodes = top ? c->sc.top_wnodes : 0;
-    return LUMO_OK;
-}
-
 lumo_status lumo_stats_get(void* ctx, lumo_stats* stats) {
     Ctx* c = static_cast<Ctx*>(ctx);
     if (!c || !stats) return LUMO_ERR_INVALID;
@@ -3762,10 +2527,10 @@ lumo_status lumo_debug_stream(void* ctx, size_t n) {
     HIPCHK(hipSetDevice(c->device));
     double* buf = nullptr;
     HIPCHK(hipMalloc(&buf, sizeof(double) * n + sizeof(double) * 4096));
-    HIPCHK(hipMemsetAsync(buf, 0, sizeof(double) * n, c->stream));
-    k_calib_read8<<<2048, BLOCK, 0, c->stream>>>(buf, n, buf + n);
-    k_calib_write8<<<2048, BLOCK, 0, c->stream>>>(buf, n);
-    const hipError_t e = hipStreamSynchronize(c->stream);
+    HIPCHK(hipMemsetAsync(buf, 0, sizeof(double) * n, c->streams[0]));
+    k_calib_read8<<<2048, BLOCK, 0, c->streams[0]>>>(buf, n, buf + n);
+    k_calib_write8<<<2048, BLOCK, 0, c->streams[0]>>>(buf, n);
+    const hipError_t e = hipStreamSynchronize(c->streams[0]);
     (void)hipFree(buf);
     HIPCHK(e);
     return LUMO_OK;
@@ -3780,25 +2545,12 @@ lumo_status lumo_debug_scan(void* ctx, const uint32_t* in, uint32_t* out, size_t
     uint32_t* buf = nullptr;
     const size_t nb = (size_t)scan_blocks((uint32_t)n);
     HIPCHK(hipMalloc(&buf, sizeof(uint32_t) * (2 * n + nb)));
-    hipError_t e = hipMemcpyAsync(buf, in, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = exclusive_scan(buf, buf + n, (uint32_t)n, buf + 2 * n, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, buf + n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipError_t e = hipMemcpyAsync(buf, in, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->streams[0]);
+    if (e == hipSuccess) e = exclusive_scan(buf, buf + n, (uint32_t)n, buf + 2 * n, c->streams[0]);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, buf + n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->streams[0]);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->streams[0]);
     (void)hipFree(buf);
     HIPCHK(e);
-    return LUMO_OK;
-}
-
-lumo_status lumo_set_option(void* ctx, int32_t option, int64_t value) {
-    Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c) return LUMO_ERR_INVALID;
-    return set_opt(*c, option, value);
-}
-
-lumo_status lumo_get_option(void* ctx, int32_t option, int64_t* value) {
-    Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c || !value || option < 0 || option >= LUMO_OPT_COUNT) return LUMO_ERR_INVALID;
-    *value = get_opt(*c, option);
     return LUMO_OK;
 }
 

@@ -1,7 +1,7 @@
 """Kernel resources of the device code as the compiler reports them (-Rpass-analysis=
 kernel-resource-usage): VGPRs, SGPRs, spilled SGPRs / VGPRs, scratch bytes per lane, waves per SIMD.
-Compiles the instantiation units for the given stack classes and kernels.hip (device only), then
-prints a markdown table.  Usage: python tools/resources.py [STK ...] > profiles/<round>/resources.md"""
+Compiles the instantiation units for the given stack classes, kernels.hip and the host-only units
+ctx.hip / upload.hip (device only), then prints a markdown table.  Usage: python tools/resources.py [STK ...] > profiles/<round>/resources.md"""
 import os
 import re
 import subprocess
@@ -38,6 +38,8 @@ def main():
     stks = sys.argv[1:] or ["0", "4"]
     units = [(f"lumo_amd/csrc/device/inst_{k}.hip", [f"-DLUMO_STK={s}"]) for s in stks for k in ("pt", "bd")]
     units.append(("lumo_amd/csrc/device/kernels.hip", []))
+    # host-only units: they must add no row
+    units += [("lumo_amd/csrc/device/ctx.hip", []), ("lumo_amd/csrc/device/upload.hip", [])]
     print("| kernel | VGPRs | SGPRs | SGPR spills | VGPR spills | scratch B/lane | waves/SIMD |")
     print("|---|---|---|---|---|---|---|")
     for src, defs in units:

@@ -17,9 +17,29 @@
 #ifndef LUMO_WHILE_WHILE  // traversal loops as while-while (bvh_traverse, kd_traverse)
 #define LUMO_WHILE_WHILE 1
 #endif
+// lumo's walks: values a thread has already formed for the same ray are kept, not formed again
+// (DESIGN.md §4 "Walk reuse").  Each knob at 0 restores the recomputation, for A/B builds; the
+// counters count lumo's logical tests either way.
+#ifndef LUMO_REUSE_SLAB  // a BVH_SAME_BOX leaf's slab interval serves its object's kd walk
+#define LUMO_REUSE_SLAB 1
+#endif
+#ifndef LUMO_REUSE_ACCEPT  // the closest-hit winner's GEO acceptance from the walk's own test
+#define LUMO_REUSE_ACCEPT 1
+#endif
+#ifndef LUMO_REUSE_RECORD  // the hit record from the accepted test's e / det (needs LUMO_REUSE_ACCEPT)
+#define LUMO_REUSE_RECORD 1
+#endif
 
 namespace lumo {
 namespace dev {
+
+// Reuse mode RM of the closest-hit entry points (shape_hit_tri): 0 the winner's GEO test runs
+// again, 1 its acceptance comes from the walk's own test, 2 that test's e / det are also returned
+// for the record.  The caller chooses: RM_REC in the kernels measured to gain from it (the lean
+// fused bounce kernel and its tail form) and in lumo_trace, which pins it to the
+// oracle; 0 everywhere else (measured slower or equal there).  RM_REC: callers that build
+// the record themselves.
+constexpr int RM_REC = LUMO_REUSE_ACCEPT ? (LUMO_REUSE_RECORD ? 2 : 1) : 0;
 
 constexpr double DINF = __builtin_huge_val();
 constexpr int NS = 4;
@@ -56,10 +76,14 @@ constexpr int TV_STRIDE = 10;  // doubles per triangle in the vertex soup (A, B,
 // upload stores the nodes breadth-first (the explicit left child and escape index make the walk
 // independent of the storage order), so the top levels of a BVH are a prefix of its array: the
 // part that LDS staging of large scenes copies (TOP staging, below).
+// A leaf's count carries BVH_SAME_BOX when the upload found that it holds exactly one un-instanced
+// kd mesh / rectangle whose kd boundary is bitwise the node's box: the walk then hands the leaf's
+// slab interval to that object's kd walk instead of testing the same box twice (kd_traverse).
 struct DBvh {
     double bmin[3], bmax[3];
     int32_t escape, first, count, left;
 };
+constexpr int32_t BVH_SAME_BOX = 1 << 30;
 
 // Object as the traversal reads it (64 B; lumo_object, 168 B, stays the record for hit records,
 // Rectangle uv and light sampling): the kd tree's boundary, its root, the triangle and kd-item
@@ -511,40 +535,23 @@ __device__ __forceinline__ void slab(const double* bmin, const double* bmax, V3 
     te = min_element(vmax(ro_max, ro_min)) * (1.0 + 2.0 * gamma_n(3));
 }
 
-// triangle.rs:63-187, GEO = false: returns t or INF.  tv: the triangle's vertex record (A, B, C).
-__device__ __forceinline__ double tri_hit_t_at(const double* tv, const RayX& r, double t_min, double t_max,
-                                               Counters& C) {
-    C.tri++;
-    const V3 A = ld3(tv), B = ld3(tv + 3), Cv = ld3(tv + 6);
-    const int kz = r.kz;
-    const V3 wi = r.wi;
-    V3 at = perm_kz(kz, A - r.o), bt = perm_kz(kz, B - r.o), ct = perm_kz(kz, Cv - r.o);
-    const V3 shear = r.shear;
-    at = at + shear * at.z;
-    bt = bt + shear * bt.z;
-    ct = ct + shear * ct.z;
-    const V3 e = V3{bt.x * ct.y - bt.y * ct.x, ct.x * at.y - ct.y * at.x, at.x * bt.y - at.y * bt.x};
-    if (min_element(e) < 0.0 && max_element(e) > 0.0) return DINF;
-    const double det = dot(e, V3{1.0, 1.0, 1.0});
-    if (det == 0.0) return DINF;
-    const double t_scaled = dot(e, V3{at.z, bt.z, ct.z}) / wi.z;
-    const bool b1 = det < 0.0 && (t_scaled > t_min * det || t_scaled < t_max * det);
-    const bool b2 = det > 0.0 && (t_scaled < t_min * det || t_scaled > t_max * det);
-    if (b1 || b2) return DINF;
-    return t_scaled / det;
-}
-__device__ __forceinline__ double tri_hit_t(const DScene& sc, int ti, const RayX& r, double t_min, double t_max,
-                                            Counters& C) {
-    return tri_hit_t_at(sc.tv + TV_STRIDE * ti, r, t_min, t_max, C);
-}
+// What an accepted triangle test leaves for the hit record: the edge functions e and their sum det,
+// from which triangle.rs forms the barycentrics e / det.
+struct TriAcc {
+    V3 e;
+    double det;
+};
 
-// triangle.rs:63-187, GEO = true: returns false on miss / self-hit reject.  FULL also builds the
-// hit record (point, normals, uv, error bounds); !FULL stops after the t <= t_min + delta_t
-// check (callers that only need acceptance and t; the record is rebuilt identically later).
-// tv: the triangle's vertex record; ti: its index in the scene's triangles (FULL only).
-template <bool FULL>
-__device__ bool tri_hit_geo_at(const DScene& sc, const double* tv, int ti, const RayX& r, double t_min, double t_max,
-                               DHit& out) {
+// triangle.rs:63-187 up to t: false on a miss (edge test, det == 0, range), else t.  tv: the
+// triangle's vertex record (A, B, C).  DT (the closest-hit walks, whose winner lumo tests again
+// with GEO = true): a test that passes also yields the GEO test's self-intersection bound delta_t,
+// formed here from the at / bt / ct / e / det of this very test by the expressions of
+// tri_hit_geo_at, and with ACC its e and det, so the winner's acceptance and record need no second
+// test.
+template <bool DT, bool ACC>
+__device__ __forceinline__ bool tri_test_at(const double* tv, const RayX& r, double t_min, double t_max, Counters& C,
+                                            double& t_out, TriAcc& acc, double& delta_t) {
+    C.tri++;
     const V3 A = ld3(tv), B = ld3(tv + 3), Cv = ld3(tv + 6);
     const int kz = r.kz;
     const V3 wi = r.wi;
@@ -561,20 +568,40 @@ __device__ bool tri_hit_geo_at(const DScene& sc, const double* tv, int ti, const
     const bool b1 = det < 0.0 && (t_scaled > t_min * det || t_scaled < t_max * det);
     const bool b2 = det > 0.0 && (t_scaled < t_min * det || t_scaled > t_max * det);
     if (b1 || b2) return false;
-    const double t = t_scaled / det;
-    const double max_z_v = rmax(rmax(fabs(at.z), fabs(bt.z)), fabs(ct.z));
-    const double delta_z = gamma_n(3) * max_z_v;
-    const double max_y_v = rmax(rmax(fabs(at.y), fabs(bt.y)), fabs(ct.y));
-    const double delta_y = gamma_n(5) * (max_y_v + max_z_v);
-    const double max_x_v = rmax(rmax(fabs(at.x), fabs(bt.x)), fabs(ct.x));
-    const double delta_x = gamma_n(5) * (max_x_v + max_z_v);
-    const double delta_e = 2.0 * (gamma_n(2) * max_x_v * max_y_v + delta_y * max_x_v + delta_x * max_y_v);
-    const double max_e = rmax(rmax(fabs(e.x), fabs(e.y)), fabs(e.z));
-    const double delta_t = 3.0 * (gamma_n(3) * max_e * max_z_v + delta_e * max_z_v + delta_z * max_e) / fabs(det);
-    if (t <= t_min + delta_t) return false;
-    out.t = t;
-    if (!FULL) return true;
-    const V3 bary = e / det;
+    t_out = t_scaled / det;
+    if constexpr (DT) {
+        const double max_z_v = rmax(rmax(fabs(at.z), fabs(bt.z)), fabs(ct.z));
+        const double delta_z = gamma_n(3) * max_z_v;
+        const double max_y_v = rmax(rmax(fabs(at.y), fabs(bt.y)), fabs(ct.y));
+        const double delta_y = gamma_n(5) * (max_y_v + max_z_v);
+        const double max_x_v = rmax(rmax(fabs(at.x), fabs(bt.x)), fabs(ct.x));
+        const double delta_x = gamma_n(5) * (max_x_v + max_z_v);
+        const double delta_e = 2.0 * (gamma_n(2) * max_x_v * max_y_v + delta_y * max_x_v + delta_x * max_y_v);
+        const double max_e = rmax(rmax(fabs(e.x), fabs(e.y)), fabs(e.z));
+        delta_t = 3.0 * (gamma_n(3) * max_e * max_z_v + delta_e * max_z_v + delta_z * max_e) / fabs(det);
+    }
+    if constexpr (ACC) acc = TriAcc{e, det};
+    return true;
+}
+// GEO = false: returns t or INF
+__device__ __forceinline__ double tri_hit_t_at(const double* tv, const RayX& r, double t_min, double t_max,
+                                               Counters& C) {
+    double t, dt;
+    TriAcc a;
+    return tri_test_at<false, false>(tv, r, t_min, t_max, C, t, a, dt) ? t : DINF;
+}
+__device__ __forceinline__ double tri_hit_t(const DScene& sc, int ti, const RayX& r, double t_min, double t_max,
+                                            Counters& C) {
+    return tri_hit_t_at(sc.tv + TV_STRIDE * ti, r, t_min, t_max, C);
+}
+
+// The record part of the GEO test (triangle.rs:131-187) of triangle ti from what its accepted test
+// left: t, and e / det of tri_test_at on the same ray and vertices.  tv: the triangle's vertex
+// record; d: the direction of the ray the test ran with.
+__device__ __forceinline__ void tri_record_at(const DScene& sc, const double* tv, int ti, const TriAcc& acc, double t,
+                                              V3 d, DHit& out) {
+    const V3 A = ld3(tv), B = ld3(tv + 3), Cv = ld3(tv + 6);
+    const V3 bary = acc.e / acc.det;
     const lumo_triangle T = sc.tris[ti];
     const V3 ng = normalize(cross(B - A, Cv - A));
     V3 ns = ng;
@@ -594,11 +621,32 @@ __device__ bool tri_hit_geo_at(const DScene& sc, const double* tv, int ti, const
                               dot(vabs(bary * V3{A.z, B.z, Cv.z}), V3{1, 1, 1})};
     out.t = t;
     out.material = T.material;
-    out.backface = dot(r.d, ng) > 0.0;
+    out.backface = dot(d, ng) > 0.0;
     out.p = xi;
     out.ns = ns;
     out.ng = ng;
     out.uv = wrap_uv(uv);
+}
+__device__ void tri_record(const DScene& sc, int ti, const TriAcc& acc, double t, V3 d, DHit& out) {
+    tri_record_at(sc, sc.tv + TV_STRIDE * ti, ti, acc, t, d, out);
+}
+
+// triangle.rs:63-187, GEO = true: returns false on miss / self-hit reject.  FULL also builds the
+// hit record (point, normals, uv, error bounds); !FULL stops after the t <= t_min + delta_t
+// check (callers that only need acceptance and t).  One copy of each expression: the test is
+// tri_test_at (its count goes to a counter of no one's: the callers count the GEO test), the
+// record tri_record_at.
+// tv: the triangle's vertex record; ti: its index in the scene's triangles (FULL only).
+template <bool FULL>
+__device__ bool tri_hit_geo_at(const DScene& sc, const double* tv, int ti, const RayX& r, double t_min, double t_max,
+                               DHit& out) {
+    Counters uncounted{0, 0, 0, 0};
+    double t, delta_t;
+    TriAcc acc;
+    if (!tri_test_at<true, FULL>(tv, r, t_min, t_max, uncounted, t, acc, delta_t)) return false;
+    if (t <= t_min + delta_t) return false;
+    out.t = t;
+    if constexpr (FULL) tri_record_at(sc, tv, ti, acc, t, r.d, out);
     return true;
 }
 template <bool FULL>
@@ -653,9 +701,19 @@ __device__ __forceinline__ DKd kd_at(const DScene& sc, int i) {
     return sc.kdp[i];
 }
 
-template <bool GEO, int STK, bool KL = false>
+// The winner of a closest-hit (GEO) kd walk: its local triangle index (-1: none) and, from the
+// test that made it the best, the GEO test's delta_t and (ACC) the record's e / det (tri_test_at).
+struct KdWin {
+    int idx;
+    double delta_t;
+    TriAcc acc;
+};
+// have_box: the caller (bvh_traverse at a BVH_SAME_BOX leaf) has just slab-tested this object's
+// boundary as its leaf box and passes the clamped interval (box_ts, box_te); see below.
+template <bool GEO, int STK, bool KL = false, int RM = 0>
 __device__ KD_INLINE double kd_traverse(const DScene& sc, const DObj& ob, const RayX& r, double t_min, double t_max,
-                              int* idx_out, Counters& C) {
+                              KdWin* win, Counters& C, bool have_box = false, double box_ts = 0.0,
+                              double box_te = 0.0) {
     const double origin[3] = {r.o.x, r.o.y, r.o.z};
     const double inv_dir[3] = {r.inv.x, r.inv.y, r.inv.z};
     int st_node[STK];
@@ -664,10 +722,20 @@ __device__ KD_INLINE double kd_traverse(const DScene& sc, const DObj& ob, const 
     double t_hit = DINF;
     int curr = ob.kd_root;
     int idx = -1;
-    double ts, te;
-    C.aabb++;
-    slab(ob.bmin, ob.bmax, r.o, r.inv, ts, te);
-    double t_start = rmax(ts, t_min), t_end = rmin(te, t_max);
+    double win_dt = 0.0;
+    TriAcc win_acc{V3{0.0, 0.0, 0.0}, 0.0};
+    C.aabb++;  // lumo's test of the kd boundary, counted whether computed here or taken over
+    // Reuse (have_box): box_ts / box_te are rmax(ts, t_min) / rmin(te, tt) of slab() on the leaf's
+    // bmin / bmax with this r.o and r.inv, where the upload found those six doubles bitwise equal
+    // to ob.bmin / ob.bmax, and the caller passes its t_min and tt on as t_min and t_max: the same
+    // expressions on the same operands as the two lines of the other branch.
+    double t_start = box_ts, t_end = box_te;
+    if (!(LUMO_REUSE_SLAB && have_box)) {
+        double ts, te;
+        slab(ob.bmin, ob.bmax, r.o, r.inv, ts, te);
+        t_start = rmax(ts, t_min);
+        t_end = rmin(te, t_max);
+    }
     const double t_end0 = t_end;
     for (;;) {
         if (t_hit < t_start) break;
@@ -704,12 +772,17 @@ __device__ KD_INLINE double kd_traverse(const DScene& sc, const DObj& ob, const 
             const int first = node.u.leaf.first, count = node.u.leaf.count;
             for (int k = 0; k < count; ++k) {
                 const int i = sc.kd_items[ob.item_base + first + k];
-                const double t = tri_hit_t(sc, ob.tri_base + i, r, t_min, t_end, C);
+                double t = DINF, dt = 0.0;
+                TriAcc a{V3{0.0, 0.0, 0.0}, 0.0};
+                if (!tri_test_at<GEO && RM >= 1, GEO && RM == 2>(sc.tv + TV_STRIDE * (ob.tri_base + i), r, t_min, t_end, C, t, a, dt))
+                    t = DINF;
                 if (GEO) {
                     if (t < t_end) {
                         t_end = t;
                         t_hit = t;
                         idx = i;
+                        if (RM >= 1) win_dt = dt;
+                        if (RM == 2) win_acc = a;
                     }
                 } else if (t < t_end) {
                     return t;
@@ -742,7 +815,7 @@ __device__ KD_INLINE double kd_traverse(const DScene& sc, const DObj& ob, const 
         }
     }
     if (GEO) {
-        *idx_out = idx;
+        *win = KdWin{idx, win_dt, win_acc};
         return idx < 0 ? DINF : t_hit;
     }
     // kd _hit::<false> ends with Hit::from_t(INF) when a leaf hit was recorded; unreachable here
@@ -798,9 +871,9 @@ __device__ __forceinline__ EF ef_div(EF a, EF b) {
     const double d0 = a.lo / b.lo, d1 = a.lo / b.hi, d2 = a.hi / b.lo, d3 = a.hi / b.hi;
     return EF{a.v / b.v, previous_float(rmin(rmin(rmin(d0, d1), d2), d3)), next_float(rmax(rmax(rmax(d0, d1), d2), d3))};
 }
-// Sphere::hit (sphere.rs:27-78); FULL also builds the record
-template <bool FULL, class OB>
-__device__ bool sphere_hit(const OB& ob, const RayX& r, double t_min, double t_max, DHit& out) {
+// Sphere::hit (sphere.rs:27-78); FULL also builds the record.  RY: Ray or RayX (only o and d are read)
+template <bool FULL, class OB, class RY>
+__device__ bool sphere_hit(const OB& ob, const RY& r, double t_min, double t_max, DHit& out) {
     const double radius = obj_radius(ob);
     const EF dx = ef(r.d.x), dy = ef(r.d.y), dz = ef(r.d.z), ox = ef(r.o.x), oy = ef(r.o.y), oz = ef(r.o.z);
     const EF radius2 = ef_mul(ef(radius), ef(radius));
@@ -867,57 +940,118 @@ constexpr int PRIM_SPHERE = -2;
 // Object::hit_t of the shape (kdtree.rs:178-180, rectangle.rs:87-89, triangle.rs:195-197)
 // FX: full feature set (instances, spheres, triangle objects, microfacet materials); scenes made
 // only of kd meshes / rectangles with Lambertian + Light materials run the FX = false kernels.
+// have_box, box_ts, box_te: kd_traverse's (set only at a BVH_SAME_BOX leaf, whose object is an
+// un-instanced kd mesh / rectangle, so they reach no other shape).
 template <int STK, int FX, bool KL = false>
 __device__ __forceinline__ double shape_hit_t(const DScene& sc, const DObj& ob, const RayX& r, double t_min,
-                                              double t_max, Counters& C) {
+                                              double t_max, Counters& C, bool have_box = false, double box_ts = 0.0,
+                                              double box_te = 0.0) {
     if constexpr (FX) {
         if (ob.type() == LUMO_OBJ_TRIANGLE) return tri_hit_t(sc, ob.tri_base, r, t_min, t_max, C);
         if (ob.type() == LUMO_OBJ_SPHERE) return sphere_hit_t(ob, r, t_min, t_max);
     }
-    return kd_traverse<false, STK, KL>(sc, ob, r, t_min, t_max, nullptr, C);
+    return kd_traverse<false, STK, KL>(sc, ob, r, t_min, t_max, nullptr, C, have_box, box_ts, box_te);
 }
 template <int STK, int FX, bool KL = false>
 __device__ __forceinline__ double object_hit_t(const DScene& sc, const DObj& ob, const RayX& r, double t_min,
-                                               double t_max, Counters& C) {
+                                               double t_max, Counters& C, bool have_box = false, double box_ts = 0.0,
+                                               double box_te = 0.0) {
     if constexpr (FX) {
         if (ob.xform() >= 0)
             return shape_hit_t<STK, FX, KL>(sc, ob, ray_local(sc.xforms[ob.xform()], r), t_min, t_max, C);
     }
-    return shape_hit_t<STK, FX, KL>(sc, ob, r, t_min, t_max, C);
+    return shape_hit_t<STK, FX, KL>(sc, ob, r, t_min, t_max, C, have_box, box_ts, box_te);
 }
 
-// Object::hit: kd GEO traversal, then the winner's GEO test (acceptance + t only; the record is
-// rebuilt by object_record).  Returns the global triangle index, PRIM_SPHERE, or -1 (miss).
-template <int STK, int FX, bool KL = false>
+// Object::hit: kd GEO traversal, then the winner's GEO test (acceptance + t only).  Returns the
+// global triangle index, PRIM_SPHERE, or -1 (miss); t and, for a triangle, the e / det that
+// object_record_acc builds the record from.
+//
+// The winner's GEO test (triangle.rs:63-187 with the call's t_min, t_max) is counted but not run
+// again: the walk's test of that triangle ran on the same ray, vertices and t_min, so its e, det,
+// t_scaled, t and delta_t are the values the GEO test would form, and it passed the edge and
+// det == 0 checks.  Range check: the walk tested with t_end in place of t_max, where t_end <= t_max
+// (t_end is fmin(te, t_max), a split t_split <= the t_end before it, or an earlier hit t < t_end;
+// a NaN t_end records no hit since t < t_end is then false).  x -> fl(x * det) is monotone, so for
+// det > 0 the walk's t_scaled <= t_end * det gives t_scaled <= t_max * det, and for det < 0 its
+// t_scaled >= t_end * det gives t_scaled >= t_max * det; the t_min side is the same comparison.
+// What remains of the GEO test is t <= t_min + delta_t, made here.  RM == 2: the caller builds
+// the record from acc (else acc is left alone and the walk keeps no e / det).
+template <int STK, int FX, bool KL = false, int RM = 0>
 __device__ __forceinline__ int shape_hit_tri(const DScene& sc, const DObj& ob, const RayX& r, double t_min,
-                                             double t_max, Counters& C, DHit& out) {
+                                             double t_max, Counters& C, double& t_out, TriAcc& acc) {
     if constexpr (FX) {
         if (ob.type() == LUMO_OBJ_TRIANGLE) {
-            C.tri++;  // the GEO test counts as a triangle test (triangle.rs:63, as the oracle counts it)
-            return tri_hit_geo<false>(sc, ob.tri_base, r, t_min, t_max, out) ? ob.tri_base : -1;
+            // the GEO test itself (counted by tri_test_at as the oracle counts it): one core for
+            // the range check, delta_t and the record's e / det
+            double t, dt;
+            TriAcc a;
+            if (!tri_test_at<true, RM == 2>(sc.tv + TV_STRIDE * ob.tri_base, r, t_min, t_max, C, t, a, dt)) return -1;
+            if (t <= t_min + dt) return -1;
+            t_out = t;
+            if (RM == 2) acc = a;
+            return ob.tri_base;
         }
-        if (ob.type() == LUMO_OBJ_SPHERE) return sphere_hit<false>(ob, r, t_min, t_max, out) ? PRIM_SPHERE : -1;
+        if (ob.type() == LUMO_OBJ_SPHERE) {
+            DHit g;
+            if (!sphere_hit<false>(ob, r, t_min, t_max, g)) return -1;
+            t_out = g.t;
+            return PRIM_SPHERE;
+        }
     }
-    int idx = -1;
-    kd_traverse<true, STK, KL>(sc, ob, r, t_min, t_max, &idx, C);
-    if (idx < 0) return -1;
+    KdWin w;
+    const double t = kd_traverse<true, STK, KL, RM>(sc, ob, r, t_min, t_max, &w, C);
+    if (w.idx < 0) return -1;
     C.tri++;
-    if (!tri_hit_geo<false>(sc, ob.tri_base + idx, r, t_min, t_max, out)) return -1;
-    return ob.tri_base + idx;
+    if constexpr (RM == 0) {  // the GEO test run again
+        DHit g;
+        if (!tri_hit_geo<false>(sc, ob.tri_base + w.idx, r, t_min, t_max, g)) return -1;
+        t_out = g.t;
+        return ob.tri_base + w.idx;
+    }
+    if (t <= t_min + w.delta_t) return -1;
+    t_out = t;
+    if (RM == 2) acc = w.acc;
+    return ob.tri_base + w.idx;
 }
-template <int STK, int FX, bool KL = false>
+template <int STK, int FX, bool KL = false, int RM = 0>
 __device__ __forceinline__ int object_hit_tri(const DScene& sc, const DObj& ob, const RayX& r, double t_min,
-                                              double t_max, Counters& C, DHit& out) {
+                                              double t_max, Counters& C, double& t_out, TriAcc& acc) {
     if constexpr (FX) {
         if (ob.xform() >= 0)
-            return shape_hit_tri<STK, FX, KL>(sc, ob, ray_local(sc.xforms[ob.xform()], r), t_min, t_max, C, out);
+            return shape_hit_tri<STK, FX, KL, RM>(sc, ob, ray_local(sc.xforms[ob.xform()], r), t_min, t_max, C,
+                                                  t_out, acc);
     }
-    return shape_hit_tri<STK, FX, KL>(sc, ob, r, t_min, t_max, C, out);
+    return shape_hit_tri<STK, FX, KL, RM>(sc, ob, r, t_min, t_max, C, t_out, acc);
 }
 
-// Full hit record of triangle `tri` of object `ob` for world ray r (the GEO test is
-// deterministic, so re-running it reproduces the accepted hit), incl. Rectangle uv
-// (rectangle.rs:74-85) and the instance transform.
+// Full hit record of triangle `tri` of object `ob` from its accepted test (object_hit_tri's t and
+// e / det) for the world ray r, incl. Rectangle uv (rectangle.rs:74-85) and the instance transform.
+// Only o and d of the ray are needed: an instance's test ran with Ray::transform's direction, the
+// same xf_apply as ray_local's.  A sphere has no e / det and runs its test again in full.
+template <int FX>
+__device__ void object_record_acc(const DScene& sc, const lumo_object& ob, int tri, const Ray& r, double t,
+                                  const TriAcc& acc, DHit& h) {
+    if constexpr (!FX) {
+        tri_record(sc, tri, acc, t, r.d, h);
+        if (ob.type == LUMO_OBJ_RECTANGLE) h.uv = wrap_uv(V2{dot(ld3(ob.b0), h.p), dot(ld3(ob.b1), h.p)});
+    } else {
+        Ray rl = r;
+        if (ob.xform >= 0) {
+            const lumo_transform& T = sc.xforms[ob.xform];
+            rl = Ray{xf_apply(T.inv, r.o, 1.0), xf_apply(T.inv, r.d, 0.0)};
+        }
+        if (ob.type == LUMO_OBJ_SPHERE)
+            sphere_hit<true>(ob, rl, 0.0, DINF, h);
+        else
+            tri_record(sc, tri, acc, t, rl.d, h);
+        if (ob.type == LUMO_OBJ_RECTANGLE) h.uv = wrap_uv(V2{dot(ld3(ob.b0), h.p), dot(ld3(ob.b1), h.p)});
+        if (ob.xform >= 0) instance_fix_hit(sc.xforms[ob.xform], ob.material_override, h);
+    }
+}
+
+// The same record for callers that kept only (object, triangle) of the hit (HitRef through HBM):
+// the GEO test is deterministic, so re-running it reproduces the accepted hit.
 template <int FX>
 __device__ void object_record(const DScene& sc, const lumo_object& ob, int tri, const RayX& r, DHit& h) {
     if constexpr (!FX) {
@@ -936,7 +1070,8 @@ __device__ void object_record(const DScene& sc, const lumo_object& ob, int tri, 
 
 // bvh.rs:315-362 (stackless, see DBvh): returns object index or -1.  TOP: nodes below n_lds are
 // read from the LDS copy nodes_lds (TOP staging), the others from `nodes`.
-template <bool GEO, int STK, int FX, bool TOP = false>
+// SLAB: a BVH_SAME_BOX leaf hands its slab interval to its object's kd walk (the caller's reuse mode)
+template <bool GEO, int STK, int FX, bool TOP = false, bool SLAB = false>
 __device__ int bvh_traverse(const DScene& sc, const DBvh* nodes, int n_nodes, const int32_t* items,
                             const DObj* objs, const RayX& r, double t_min, double t_max, Counters& C,
                             double* t_found = nullptr, const DBvh* nodes_lds = nullptr, int n_lds = 0) {
@@ -950,9 +1085,9 @@ __device__ int bvh_traverse(const DScene& sc, const DBvh* nodes, int n_nodes, co
     // together instead of one lane's at a time.  Each lane's node / object sequence is lumo's.
     for (;;) {
         int count = 0;
+        double ts = 0.0, te = 0.0;  // the leaf's clamped slab interval, for a BVH_SAME_BOX leaf's kd walk
         while (curr >= 0) {
             const DBvh& node = (TOP && curr < n_lds) ? nodes_lds[curr] : nodes[curr];
-            double ts, te;
             C.aabb++;
             slab(node.bmin, node.bmax, r.o, inv_dir, ts, te);
             ts = rmax(ts, t_min);
@@ -979,15 +1114,18 @@ __device__ int bvh_traverse(const DScene& sc, const DBvh* nodes, int n_nodes, co
         ts = rmax(ts, t_min);
         te = rmin(te, tt);
         if (ts <= te) {
-            const int count = node.count;
+            int count = node.count;
             if (count == 0) {
                 curr = node.left;
                 continue;
             }
 #endif
+            // BVH_SAME_BOX (one object, count 1): tt is still the tt of the slab test above
+            const bool same_box = LUMO_REUSE_SLAB && SLAB && (count & BVH_SAME_BOX) != 0;
+            count &= ~BVH_SAME_BOX;
             for (int k = 0; k < count; ++k) {
                 const int i = items[node.first + k];
-                const double t = object_hit_t<STK, FX, TOP>(sc, objs[i], r, t_min, tt, C);
+                const double t = object_hit_t<STK, FX, TOP>(sc, objs[i], r, t_min, tt, C, same_box, ts, te);
                 if (GEO) {
                     if (t < tt) {
                         tt = t;
@@ -1005,14 +1143,14 @@ __device__ int bvh_traverse(const DScene& sc, const DBvh* nodes, int n_nodes, co
 }
 
 // BVH::hit_t (bvh.rs:371-374)
-template <int STK, int FX, bool TOP = false>
+template <int STK, int FX, bool TOP = false, bool SLAB = false>
 __device__ __forceinline__ double bvh_hit_t(const DScene& sc, const DBvh* nodes, int n, const int32_t* items,
                                             const DObj* objs, const RayX& r, double t_min, double t_max,
                                             Counters& C, const DBvh* nodes_lds = nullptr, int n_lds = 0) {
     // bvh.rs:371-374 re-runs objects[idx].hit_t(r, t_min, t_max); in any-hit mode the traversal
     // called exactly that (tt == t_max), so its value is reused.
     double t = DINF;
-    const int idx = bvh_traverse<false, STK, FX, TOP>(sc, nodes, n, items, objs, r, t_min, t_max, C, &t, nodes_lds, n_lds);
+    const int idx = bvh_traverse<false, STK, FX, TOP, SLAB>(sc, nodes, n, items, objs, r, t_min, t_max, C, &t, nodes_lds, n_lds);
     if (idx < 0) return DINF;
     return t;
 }
@@ -1337,31 +1475,43 @@ __device__ __forceinline__ bool wide_occluded(const DScene& sc, const RayX& r, d
     return wide_walk<true, FX, TOP, OC>(sc, sc.w_lroot, sc.tlights, sc.w_lblas, r, 0.0, t_max, C).t < t_max;
 }
 // OC: the wide walks' object leaves as calls (wide_sphere_t_call); no effect on lumo's walks
-template <int STK, int FX, bool TOP = false, bool OC = false>
-__device__ HitRef scene_hit(const DScene& sc, const RayX& r, Counters& C) {
+// RM == 2 (lumo's walks only, STK != 0): acc receives e / det of the returned triangle's accepted
+// test, for hit_record_acc
+template <int STK, int FX, bool TOP = false, bool OC = false, int RM = 0>
+__device__ HitRef scene_hit(const DScene& sc, const RayX& r, Counters& C, TriAcc& acc) {
     if constexpr (STK == 0) {
         return wide_scene_hit<FX, TOP, OC>(sc, r, C);
     } else {
     HitRef h{DINF, 0, -1, -1};
     double t_max = DINF;
-    DHit g;
-    int oi = bvh_traverse<true, STK, FX, TOP>(sc, sc.onodes, sc.n_onodes, sc.oitems, sc.tobjs, r, 0.0, t_max, C, nullptr,
+    // object_hit_tri writes t and e / det only when it accepts a hit
+    double gt = DINF;
+    TriAcc ga{V3{0.0, 0.0, 0.0}, 0.0};
+    int oi = bvh_traverse<true, STK, FX, TOP, RM != 0>(sc, sc.onodes, sc.n_onodes, sc.oitems, sc.tobjs, r, 0.0, t_max, C, nullptr,
                                               sc.onodes_lds, sc.n_onodes_lds);
     if (oi >= 0) {
-        const int tri = object_hit_tri<STK, FX, TOP>(sc, sc.tobjs[oi], r, 0.0, t_max, C, g);
+        const int tri = object_hit_tri<STK, FX, TOP, RM>(sc, sc.tobjs[oi], r, 0.0, t_max, C, gt, ga);
         if (tri != -1) {
-            h = HitRef{g.t, 1, oi, tri};
-            t_max = g.t;
+            h = HitRef{gt, 1, oi, tri};
+            t_max = gt;
         }
     }
-    const int li = bvh_traverse<true, STK, FX, TOP>(sc, sc.lnodes, sc.n_lnodes, sc.litems, sc.tlights, r, 0.0, t_max, C,
+    const int li = bvh_traverse<true, STK, FX, TOP, RM != 0>(sc, sc.lnodes, sc.n_lnodes, sc.litems, sc.tlights, r, 0.0, t_max, C,
                                                     nullptr, sc.lnodes_lds, sc.n_lnodes_lds);
     if (li >= 0) {
-        const int tri = object_hit_tri<STK, FX, TOP>(sc, sc.tlights[li], r, 0.0, t_max, C, g);
-        if (tri != -1) h = HitRef{g.t, 2, li, tri};
+        const int tri = object_hit_tri<STK, FX, TOP, RM>(sc, sc.tlights[li], r, 0.0, t_max, C, gt, ga);
+        if (tri != -1) h = HitRef{gt, 2, li, tri};
     }
+    if (RM == 2) acc = ga;
     return h;
     }
+}
+
+// Scene::hit for callers that keep only (t, kind, object, triangle)
+template <int STK, int FX, bool TOP = false, bool OC = false>
+__device__ __forceinline__ HitRef scene_hit(const DScene& sc, const RayX& r, Counters& C) {
+    TriAcc unused;  // never written: RM == 0
+    return scene_hit<STK, FX, TOP, OC, 0>(sc, r, C, unused);
 }
 
 // Rebuild the full hit record of a closest hit (the GEO test is deterministic).
@@ -1370,27 +1520,42 @@ __device__ __forceinline__ void hit_record(const DScene& sc, const HitRef& hr, c
     const lumo_object& ob = hr.kind == 1 ? sc.objs[hr.obj] : sc.lights[hr.obj];
     object_record<FX>(sc, ob, hr.tri, r, h);
 }
+// The full hit record of a closest hit from what scene_hit kept of its accepted test.
+template <int FX>
+__device__ __forceinline__ void hit_record_acc(const DScene& sc, const HitRef& hr, const TriAcc& acc, const Ray& r,
+                                               DHit& h) {
+    const lumo_object& ob = hr.kind == 1 ? sc.objs[hr.obj] : sc.lights[hr.obj];
+    object_record_acc<FX>(sc, ob, hr.tri, r, hr.t, acc, h);
+}
 
-// Scene::hit_light (scene.rs:165-189): returns true and the light hit if visible.
-template <int STK, int FX, bool TOP = false>
+// Scene::hit_light (scene.rs:165-189): returns true and the light hit if visible.  With RM == 2
+// lumo's walks build the record from the e / det of the light's own accepted test
+// (object_record_acc); the wide form runs the GEO test again for it (e / det held across its walk did not fit the registers of
+// the wide kernels).
+template <int STK, int FX, bool TOP = false, int RM = 0>
 __device__ bool scene_hit_light(const DScene& sc, const RayX& r, int light, DHit& lh, Counters& C) {
+    double t = DINF;
+    TriAcc acc{V3{0.0, 0.0, 0.0}, 0.0};
     if constexpr (STK == 0) {
-        const int tri = object_hit_tri<kd_stk<STK>(), FX, false>(sc, sc.tlights[light], r, 0.0, DINF, C, lh);
-        if (tri == -1 || wide_occluded<FX, TOP>(sc, r, lh.t - EPSILON, C)) return false;
+        const int tri = object_hit_tri<kd_stk<STK>(), FX, false>(sc, sc.tlights[light], r, 0.0, DINF, C, t, acc);
+        if (tri == -1 || wide_occluded<FX, TOP>(sc, r, t - EPSILON, C)) return false;
         object_record<FX>(sc, sc.lights[light], tri, r, lh);
         return true;
     } else {
-    const int tri = object_hit_tri<STK, FX, TOP>(sc, sc.tlights[light], r, 0.0, DINF, C, lh);
+    const int tri = object_hit_tri<STK, FX, TOP, RM>(sc, sc.tlights[light], r, 0.0, DINF, C, t, acc);
     if (tri == -1) return false;
-    const double t_max = lh.t - EPSILON;
-    if (bvh_hit_t<STK, FX, TOP>(sc, sc.onodes, sc.n_onodes, sc.oitems, sc.tobjs, r, 0.0, t_max, C, sc.onodes_lds,
+    const double t_max = t - EPSILON;
+    if (bvh_hit_t<STK, FX, TOP, RM != 0>(sc, sc.onodes, sc.n_onodes, sc.oitems, sc.tobjs, r, 0.0, t_max, C, sc.onodes_lds,
                                 sc.n_onodes_lds) < t_max)
         return false;
-    if (bvh_hit_t<STK, FX, TOP>(sc, sc.lnodes, sc.n_lnodes, sc.litems, sc.tlights, r, 0.0, t_max, C, sc.lnodes_lds,
+    if (bvh_hit_t<STK, FX, TOP, RM != 0>(sc, sc.lnodes, sc.n_lnodes, sc.litems, sc.tlights, r, 0.0, t_max, C, sc.lnodes_lds,
                                 sc.n_lnodes_lds) < t_max)
         return false;
-    // visible: build the light hit record (same GEO test, now in full)
-    object_record<FX>(sc, sc.lights[light], tri, r, lh);
+    // visible: the light hit record
+    if constexpr (RM == 2)
+        object_record_acc<FX>(sc, sc.lights[light], tri, Ray{r.o, r.d}, t, acc, lh);
+    else
+        object_record<FX>(sc, sc.lights[light], tri, r, lh);
     return true;
     }
 }
@@ -1399,15 +1564,16 @@ __device__ bool scene_hit_light(const DScene& sc, const RayX& r, int light, DHit
 // object_record rebuilds the record (the same GEO test).
 template <int STK, int FX, bool TOP = false, bool OC = false>
 __device__ int scene_hit_light_tri(const DScene& sc, const RayX& r, int light, Counters& C) {
-    DHit lh;
+    double t = DINF;
+    TriAcc acc;
     if constexpr (STK == 0) {
-        const int tri = object_hit_tri<kd_stk<STK>(), FX, false>(sc, sc.tlights[light], r, 0.0, DINF, C, lh);
-        if (tri == -1 || wide_occluded<FX, TOP, OC>(sc, r, lh.t - EPSILON, C)) return -1;
+        const int tri = object_hit_tri<kd_stk<STK>(), FX, false>(sc, sc.tlights[light], r, 0.0, DINF, C, t, acc);
+        if (tri == -1 || wide_occluded<FX, TOP, OC>(sc, r, t - EPSILON, C)) return -1;
         return tri;
     } else {
-    const int tri = object_hit_tri<STK, FX, TOP>(sc, sc.tlights[light], r, 0.0, DINF, C, lh);
+    const int tri = object_hit_tri<STK, FX, TOP, 0>(sc, sc.tlights[light], r, 0.0, DINF, C, t, acc);
     if (tri == -1) return -1;
-    const double t_max = lh.t - EPSILON;
+    const double t_max = t - EPSILON;
     if (bvh_hit_t<STK, FX, TOP>(sc, sc.onodes, sc.n_onodes, sc.oitems, sc.tobjs, r, 0.0, t_max, C, sc.onodes_lds,
                                 sc.n_onodes_lds) < t_max)
         return -1;

@@ -618,6 +618,11 @@ __global__ __launch_bounds__(BLOCK) void k_nee_fold(Paths S, QState nxt, int ns)
 // thread runs its path to the end inside one launch; per-path results do not depend on the
 // other paths, so they are unchanged.
 
+// Reuse mode (dscene.h RM) of the fused bounce kernel and its tail form: the lean kernels gain from
+// it; the full-feature ones (FX != 0) measured 7 % slower with it (registers) and keep lumo's calls.
+template <int FX>
+constexpr int RM_BOUNCE = FX == 0 ? RM_REC : 0;
+
 // One NEE record (integrator.rs:100-137) held in registers: spawned ray, bsdf_f, bsdf_pdf and
 // the shading cosine towards its direction.
 struct NeeRec {
@@ -646,7 +651,7 @@ __device__ __forceinline__ DColor shadow_record_r(const DScene& sc, const NeeRec
     const RayX ri = rayx(R.ray);
     DHit hi;
     DColor out = cfill(0.0);
-    if (scene_hit_light<STK, FX>(sc, ri, li, hi, C)) {
+    if (scene_hit_light<STK, FX, false, RM_BOUNCE<FX>>(sc, ri, li, hi, C)) {
         const lumo_object& Lo = sc.lights[li];
         const double p_lig = light_pdf<FX>(sc, Lo, ri, hi.p, hi.ng);
         const double p_sct = R.pdf;
@@ -677,7 +682,7 @@ __device__ __forceinline__ DColor shadow_record_lds(const DScene& sc, const Ray&
     const RayX ri = rayx(ray);
     DHit hi;
     DColor out = cfill(0.0);
-    if (scene_hit_light<STK, FX>(sc, ri, li, hi, C)) {
+    if (scene_hit_light<STK, FX, false, RM_BOUNCE<FX>>(sc, ri, li, hi, C)) {
         const lumo_object& Lo = sc.lights[li];
         const double p_lig = light_pdf<FX>(sc, Lo, ri, hi.p, hi.ng);
         const double p_sct = pdf;
@@ -718,11 +723,15 @@ template <int STK, int FX>
 __device__ __forceinline__ bool bounce_path(const DScene& sc, const double* delta, PathReg& P, Counters& Cc,
                                             Counters& Cs) {
     const RayX rx = rayx(P.ro);
-    const HitRef hr = scene_hit<STK, FX>(sc, rx, Cc);  // Scene::hit (k_closest_q)
+    TriAcc acc{V3{0.0, 0.0, 0.0}, 0.0};
+    const HitRef hr = scene_hit<STK, FX, false, false, RM_BOUNCE<FX>>(sc, rx, Cc, acc);  // Scene::hit (k_closest_q)
     P.queries += 1u;
     if (hr.kind == 0) return false;
     DHit ho;
-    hit_record<FX>(sc, hr, rx, ho);
+    if constexpr (STK == 0 || RM_BOUNCE<FX> != 2)  // the wide walks keep no e / det: the GEO test again
+        hit_record<FX>(sc, hr, rx, ho);
+    else
+        hit_record_acc<FX>(sc, hr, acc, P.ro, ho);
     const lumo_material m = sc.mats[ho.material];
     const V3 wo = -P.ro.d;
     const double rand_u = xs_float(P.rng);
@@ -892,7 +901,10 @@ __global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_
             LUMO_PHASE(3);
             // phase 1: Scene::hit (k_closest_q)
             HitRef hr{DINF, 0, -1, -1};
-            if (live) hr = scene_hit<STK, FX>(sc, rayx(Ray{qv3(cur, QD_O, q), qv3(cur, QD_D, q)}), Cc);
+            TriAcc hacc{V3{0.0, 0.0, 0.0}, 0.0};  // e / det of the hit's accepted test, for its record in phase 2
+            if (live)
+                hr = scene_hit<STK, FX, false, false, RM_BOUNCE<FX>>(sc, rayx(Ray{qv3(cur, QD_O, q), qv3(cur, QD_D, q)}), Cc,
+                                                                hacc);
             LUMO_PHASE(0);
             // phase 2: the bounce of k_shade_q (NS1) with the pair's records kept in registers
             PathReg P{};
@@ -907,7 +919,10 @@ __global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_
                 P.queries += 1u;
                 if (hr.kind != 0) {
                     DHit ho;
-                    hit_record<FX>(sc, hr, rayx(P.ro), ho);
+                    if constexpr (STK == 0 || RM_BOUNCE<FX> != 2)  // the wide walks keep no e / det: the GEO test again
+                        hit_record<FX>(sc, hr, rayx(P.ro), ho);
+                    else  // P.ro is the ray phase 1 walked with, re-read from the same queue entry
+                        hit_record_acc<FX>(sc, hr, hacc, P.ro, ho);
                     const lumo_material m = sc.mats[ho.material];
                     const V3 wo = -P.ro.d;
                     const double rand_u = xs_float(P.rng);
@@ -1068,7 +1083,8 @@ __global__ __launch_bounds__(TOP ? TOP_BLOCK : BLOCK) void k_trace(DScene sc0, c
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const RayX r = rayx(Ray{ldv3(o, i), ldv3(d, i)});
         if (!any_hit) {
-            const HitRef h = scene_hit<STK, true, TOP>(sc, r, C);
+            TriAcc acc;  // lumo_trace runs the reuse paths (its results and counters are pinned to the oracle)
+            const HitRef h = scene_hit<STK, true, TOP, false, RM_REC>(sc, r, C, acc);
             t_out[i] = h.t;
             kind_out[i] = h.kind;
             obj_out[i] = h.obj;
@@ -1076,7 +1092,7 @@ __global__ __launch_bounds__(TOP ? TOP_BLOCK : BLOCK) void k_trace(DScene sc0, c
         } else {
             DHit lh;
             const int li = light[i];
-            const bool vis = scene_hit_light<STK, true, TOP>(sc, r, li, lh, C);
+            const bool vis = scene_hit_light<STK, true, TOP, RM_REC>(sc, r, li, lh, C);
             t_out[i] = vis ? lh.t : DINF;
             kind_out[i] = vis ? 2 : 0;
             obj_out[i] = vis ? li : -1;

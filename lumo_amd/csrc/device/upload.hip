@@ -86,9 +86,12 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
     chk(upload(*c, d->kd_nodes, (size_t)d->num_kd_nodes, &s.kd));
     chk(upload(*c, d->kd_items, (size_t)d->num_kd_items, &s.kd_items));
     // device BVHs (DBvh, dscene.h): right child -> escape index (lumo's preorder successor of the
-    // subtree), left child explicit, nodes stored breadth-first so the top levels are a prefix
+    // subtree), left child explicit, nodes stored breadth-first so the top levels are a prefix.
+    // A leaf of exactly one un-instanced kd mesh / rectangle whose kd boundary is bitwise the
+    // node's box gets BVH_SAME_BOX in its count: the walk tests that box once (bvh_traverse).
     bool bvh_ok = true;
-    auto escapes = [&](const lumo_bvh_node* nodes, int n, std::vector<DBvh>& out) {
+    auto escapes = [&](const lumo_bvh_node* nodes, int n, const int32_t* items, int n_items, const lumo_object* objs,
+                       int n_objs, std::vector<DBvh>& out) {
         out.assign(n > 0 ? n : 0, DBvh{});
         if (n <= 0) return;
         std::vector<int32_t> esc(n, -1);
@@ -135,11 +138,17 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
             o.left = nodes[i].count == 0 ? at[i + 1] : -1;
             o.first = nodes[i].first;
             o.count = nodes[i].count;
+            if (o.count == 1 && o.first >= 0 && o.first < n_items && items[o.first] >= 0 && items[o.first] < n_objs) {
+                const lumo_object& ob = objs[items[o.first]];
+                if ((ob.type == LUMO_OBJ_KDMESH || ob.type == LUMO_OBJ_RECTANGLE) && ob.xform < 0 &&
+                    std::memcmp(ob.bmin, o.bmin, sizeof(o.bmin)) == 0 && std::memcmp(ob.bmax, o.bmax, sizeof(o.bmax)) == 0)
+                    o.count |= BVH_SAME_BOX;
+            }
         }
     };
     std::vector<DBvh> obvh, lbvh;
-    escapes(d->object_nodes, d->num_object_nodes, obvh);
-    escapes(d->light_nodes, d->num_light_nodes, lbvh);
+    escapes(d->object_nodes, d->num_object_nodes, d->object_items, d->num_object_items, d->objects, d->num_objects, obvh);
+    escapes(d->light_nodes, d->num_light_nodes, d->light_items, d->num_light_items, d->lights, d->num_lights, lbvh);
     if (!bvh_ok) {
         free_scene(*c);
         return LUMO_ERR_INVALID;

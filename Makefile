@@ -74,7 +74,7 @@ sanitize: build/sanitize/lumo_sanitize
 	    ./build/sanitize/lumo_sanitize
 
 # A/B builds of the device code (perf experiments, loaded with LUMO_AMD_LIB=<path>):
-#   make variant NAME=rs0 DEVFLAGS=-DLUMO_KD_REG=0   ->  lumo_amd/var/liblumo_amd_rs0.so
+#   make variant NAME=slab0 DEVFLAGS=-DLUMO_REUSE_SLAB=0   ->  lumo_amd/var/liblumo_amd_slab0.so
 variant:
 	@mkdir -p lumo_amd/var
 	$(MAKE) BUILD=build/var_$(NAME) LIB=lumo_amd/var/liblumo_amd_$(NAME).so DEVFLAGS="$(DEVFLAGS)" lumo_amd/var/liblumo_amd_$(NAME).so

@@ -105,7 +105,6 @@ struct Opts {
 };
 
 struct Ctx {
-    BounceArgs* bargs = nullptr;  // one k_bounce_q argument block per stream (same index as `streams`)
     int device = 0;
     size_t lds_cu = 160 * 1024;     // LDS per CU (hipDeviceProp_t::maxSharedMemoryPerMultiProcessor)
     size_t lds_block = 160 * 1024;  // LDS one block may allocate (sharedMemPerBlock)

@@ -240,11 +240,6 @@ lumo_status lumo_create(int device, void** ctx_out) {
         delete c;
         return LUMO_ERR_OOM;
     }
-    if (hipMalloc(reinterpret_cast<void**>(&c->bargs), 4 * sizeof(BounceArgs)) != hipSuccess) {
-        (void)hipStreamDestroy(c->streams[0]);
-        delete c;
-        return LUMO_ERR_OOM;
-    }
     // the environment's overrides of the defaults: integers; the 0 / 1 switches also take
     // on / off, true / false, yes / no.  A value that does not parse is ignored and an
     // out-of-range one clamped, each with a one-line warning on stderr
@@ -294,7 +289,6 @@ void lumo_destroy(void* ctx) {
         if (b.p) (void)hipFree(b.p);
     for (int i = 0; i < Ctx::SNAP_RING; ++i) (void)hipEventDestroy(c->snap_ev[i]);
     if (c->snap) (void)hipHostFree(c->snap);
-    if (c->bargs) (void)hipFree(c->bargs);
     if (c->bd_totals_h) (void)hipHostFree(c->bd_totals_h);
     for (int i = 0; i < 4; ++i) (void)hipEventDestroy(c->bd_ev[i]);
     for (int i = 0; i < 4; ++i) {

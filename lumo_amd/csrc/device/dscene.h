@@ -14,9 +14,6 @@
 #include "../common/vec.h"
 #include "../common/wbvh.h"
 
-#ifndef LUMO_WHILE_WHILE  // traversal loops as while-while (bvh_traverse, kd_traverse)
-#define LUMO_WHILE_WHILE 1
-#endif
 // lumo's walks: values a thread has already formed for the same ray are kept, not formed again
 // (DESIGN.md §4 "Walk reuse").  Each knob at 0 restores the recomputation, for A/B builds; the
 // counters count lumo's logical tests either way.
@@ -740,7 +737,6 @@ __device__ KD_INLINE double kd_traverse(const DScene& sc, const DObj& ob, const 
     for (;;) {
         if (t_hit < t_start) break;
         DKd node = kd_at<KL>(sc, curr);
-#if LUMO_WHILE_WHILE
         // while-while (Aila & Laine 2009): descend interior nodes until this lane is at a leaf
         // before any lane tests triangles, so the leaves of a wave's lanes are processed together.
         // t_start and t_hit change only at a leaf or a pop, so the check above still runs before
@@ -766,53 +762,30 @@ __device__ KD_INLINE double kd_traverse(const DScene& sc, const DObj& ob, const 
             }
             node = kd_at<KL>(sc, curr);
         }
-#endif
-        const int axis = node.meta & 3;
-        if (axis == 3) {
-            const int first = node.u.leaf.first, count = node.u.leaf.count;
-            for (int k = 0; k < count; ++k) {
-                const int i = sc.kd_items[ob.item_base + first + k];
-                double t = DINF, dt = 0.0;
-                TriAcc a{V3{0.0, 0.0, 0.0}, 0.0};
-                if (!tri_test_at<GEO && RM >= 1, GEO && RM == 2>(sc.tv + TV_STRIDE * (ob.tri_base + i), r, t_min, t_end, C, t, a, dt))
-                    t = DINF;
-                if (GEO) {
-                    if (t < t_end) {
-                        t_end = t;
-                        t_hit = t;
-                        idx = i;
-                        if (RM >= 1) win_dt = dt;
-                        if (RM == 2) win_acc = a;
-                    }
-                } else if (t < t_end) {
-                    return t;
+        const int first = node.u.leaf.first, count = node.u.leaf.count;
+        for (int k = 0; k < count; ++k) {
+            const int i = sc.kd_items[ob.item_base + first + k];
+            double t = DINF, dt = 0.0;
+            TriAcc a{V3{0.0, 0.0, 0.0}, 0.0};
+            if (!tri_test_at<GEO && RM >= 1, GEO && RM == 2>(sc.tv + TV_STRIDE * (ob.tri_base + i), r, t_min, t_end, C, t, a, dt))
+                t = DINF;
+            if (GEO) {
+                if (t < t_end) {
+                    t_end = t;
+                    t_hit = t;
+                    idx = i;
+                    if (RM >= 1) win_dt = dt;
+                    if (RM == 2) win_acc = a;
                 }
-            }
-            if (sp == 0) break;
-            sp--;
-            curr = kst_node<KL>(sc, st_node, sp);
-            t_start = kst_t<KL>(sc, st_ts, sp);
-            t_end = sp == 0 ? t_end0 : kst_t<KL>(sc, st_ts, sp - 1);
-        } else {
-            C.kd++;
-            const int ax = axis;
-            const double point = node.u.point;
-            const int right = node.meta >> 2;
-            const double t_split = (point - origin[ax]) * inv_dir[ax];
-            const bool left_first = origin[ax] < point || (origin[ax] == point && inv_dir[ax] <= 0.0);
-            const int first = left_first ? node.left : right;
-            const int second = left_first ? right : node.left;
-            if (t_split > t_end || t_split <= 0.0) {
-                curr = first;
-            } else if (t_split < t_start) {
-                curr = second;
-            } else {
-                curr = first;
-                kst_push<KL>(sc, st_node, st_ts, sp, second, t_split);
-                t_end = t_split;
-                sp++;
+            } else if (t < t_end) {
+                return t;
             }
         }
+        if (sp == 0) break;
+        sp--;
+        curr = kst_node<KL>(sc, st_node, sp);
+        t_start = kst_t<KL>(sc, st_ts, sp);
+        t_end = sp == 0 ? t_end0 : kst_t<KL>(sc, st_ts, sp - 1);
     }
     if (GEO) {
         *win = KdWin{idx, win_dt, win_acc};
@@ -1079,7 +1052,6 @@ __device__ int bvh_traverse(const DScene& sc, const DBvh* nodes, int n_nodes, co
     const V3 inv_dir = r.inv;
     int curr = 0, idx = -1;
     double tt = t_max;
-#if LUMO_WHILE_WHILE
     // while-while (Aila & Laine 2009): every lane first advances to its next leaf whose box
     // passes (tt changes only in a leaf), then the lanes' object tests (kd traversals) run
     // together instead of one lane's at a time.  Each lane's node / object sequence is lumo's.
@@ -1104,37 +1076,20 @@ __device__ int bvh_traverse(const DScene& sc, const DBvh* nodes, int n_nodes, co
         }
         if (curr < 0) break;
         const DBvh& node = (TOP && curr < n_lds) ? nodes_lds[curr] : nodes[curr];
-        {
-#else
-    while (curr >= 0) {
-        const DBvh& node = (TOP && curr < n_lds) ? nodes_lds[curr] : nodes[curr];
-        double ts, te;
-        C.aabb++;
-        slab(node.bmin, node.bmax, r.o, inv_dir, ts, te);
-        ts = rmax(ts, t_min);
-        te = rmin(te, tt);
-        if (ts <= te) {
-            int count = node.count;
-            if (count == 0) {
-                curr = node.left;
-                continue;
-            }
-#endif
-            // BVH_SAME_BOX (one object, count 1): tt is still the tt of the slab test above
-            const bool same_box = LUMO_REUSE_SLAB && SLAB && (count & BVH_SAME_BOX) != 0;
-            count &= ~BVH_SAME_BOX;
-            for (int k = 0; k < count; ++k) {
-                const int i = items[node.first + k];
-                const double t = object_hit_t<STK, FX, TOP>(sc, objs[i], r, t_min, tt, C, same_box, ts, te);
-                if (GEO) {
-                    if (t < tt) {
-                        tt = t;
-                        idx = i;
-                    }
-                } else if (t < tt) {
-                    if (t_found) *t_found = t;
-                    return i;
+        // BVH_SAME_BOX (one object, count 1): tt is still the tt of the slab test above
+        const bool same_box = LUMO_REUSE_SLAB && SLAB && (count & BVH_SAME_BOX) != 0;
+        count &= ~BVH_SAME_BOX;
+        for (int k = 0; k < count; ++k) {
+            const int i = items[node.first + k];
+            const double t = object_hit_t<STK, FX, TOP>(sc, objs[i], r, t_min, tt, C, same_box, ts, te);
+            if (GEO) {
+                if (t < tt) {
+                    tt = t;
+                    idx = i;
                 }
+            } else if (t < tt) {
+                if (t_found) *t_found = t;
+                return i;
             }
         }
         curr = node.escape;

@@ -946,8 +946,6 @@ void launch_trav(Ctx& c, uint64_t count, F&& f, hipStream_t stream = nullptr, bo
     const int grid_full = ceil_div(count, BLOCK);
     TravLaunch l{lds ? std::min(grid_full, (int)c.o.lds_grid) : grid_full, lds ? (size_t)c.sc.hot_bytes : 0, lds,
                  c.sc.full, stream ? stream : c.streams[0]};
-    for (int i = 0; i < 4; ++i)
-        if (l.sm == c.streams[i]) l.args = c.bargs + i;
     if (top) {
         l.top = true;
         l.grid = std::min(ceil_div(count, TOP_BLOCK), (int)c.o.top_grid);

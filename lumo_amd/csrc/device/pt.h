@@ -54,6 +54,96 @@ __device__ __forceinline__ void qc(const QState& Q, int k, size_t q, const DColo
     for (int i = 0; i < NS; ++i) Q.D(k + i, q) = c.s[i];
 }
 
+// A path between bounces, in registers (one QState entry).
+struct PathReg {
+    Ray ro;
+    DColor g, rad;
+    double L[NS];
+    Xorshift rng;
+    int32_t slot, task;
+    uint32_t depth, flags, queries;
+};
+__device__ __forceinline__ PathReg load_path(const QState& cur, uint32_t q) {
+    PathReg P;
+    P.slot = cur.I(QI_SLOT, q);
+    P.task = cur.I(QI_TASK, q);
+    P.depth = (uint32_t)cur.I(QI_DEPTH, q);
+    P.flags = (uint32_t)cur.I(QI_FLAGS, q);
+    P.queries = (uint32_t)cur.I(QI_QUERIES, q);
+    P.ro = Ray{qv3(cur, QD_O, q), qv3(cur, QD_D, q)};
+    P.g = qc(cur, QD_G, q);
+    P.rad = qc(cur, QD_R, q);
+    if (P.flags & QF_PENDING) P.rad = P.rad + qc(cur, QD_P, q);  // the previous bounce's NEE term
+    for (int i = 0; i < NS; ++i) P.L[i] = cur.D(QD_L + i, q);
+    P.rng = Xorshift{cur.R(0, q), cur.R(1, q)};
+    return P;
+}
+// A continuing path (continue_path returned true) into entry np of the next queue, along ray rn;
+// pending: this bounce's NEE term is still to be delivered into the entry (QD_P).
+__device__ __forceinline__ void store_next(const QState& nxt, uint32_t np, const PathReg& P, const Ray& rn, bool pending) {
+    qv3(nxt, QD_O, np, rn.o);
+    qv3(nxt, QD_D, np, rn.d);
+    qc(nxt, QD_G, np, P.g);
+    qc(nxt, QD_R, np, P.rad);
+    for (int i = 0; i < NS; ++i) nxt.D(QD_L + i, np) = P.L[i];
+    nxt.R(0, np) = P.rng.hi;
+    nxt.R(1, np) = P.rng.lo;
+    nxt.I(QI_SLOT, np) = P.slot;
+    nxt.I(QI_TASK, np) = P.task;
+    nxt.I(QI_DEPTH, np) = (int32_t)(P.depth + 1u);
+    nxt.I(QI_FLAGS, np) = (int32_t)(P.flags | (pending ? (uint32_t)QF_PENDING : 0u));
+    nxt.I(QI_QUERIES, np) = (int32_t)P.queries;
+}
+// The final values of a path that ends (FilmSample, path_trace.rs:79-81); with_rad = false when a
+// later kernel adds the bounce's NEE term to the radiance before storing it.
+__device__ __forceinline__ void store_final(const Paths& S, const PathReg& P, bool with_rad = true) {
+    for (int i = 0; i < NS; ++i) S.lam[4 * P.slot + i] = P.L[i];
+    S.depth[P.slot] = P.depth;
+    S.queries[P.slot] = P.queries;
+    if (with_rad) stc(S.rad, P.slot, P.rad);
+}
+
+// The BSDF sample of a bounce at hit ho of material m (path_trace.rs:18-41): two draws, the
+// sample (it may terminate wavelengths of P.L), and on failure the emission seen after a specular
+// bounce.  Returns 0: no direction sampled (the path ends), 1: wi sampled at a delta material (no
+// NEE), 2: wi sampled and the bounce has NEE pairs (`resolve`).
+template <int FX>
+__device__ __forceinline__ int sample_step(const DScene& sc, const lumo_material& m, const DHit& ho, V3 wo, PathReg& P,
+                                           V3& wi) {
+    const double rand_u = xs_float(P.rng);
+    const V2 rsq = xs_vec2(P.rng);
+    if (!bsdf_sample<FX>(sc, m, ho, wo, P.L, rand_u, rsq, wi)) {
+        if (P.flags & QF_SPECULAR) P.rad = P.rad + P.g * emit<FX>(sc, m, P.L, ho.backface, ho.uv);
+        return 0;
+    }
+    return mat_is_delta<FX>(sc, m, P.L) ? 1 : 2;
+}
+// The continuation along a sampled wi (path_trace.rs:42-77): spawn, throughput, Russian roulette
+// against the task's delta.  Returns whether the path goes on along rn; P then holds the next
+// bounce's throughput, RNG state and flags (depth still this bounce's).
+template <int FX>
+__device__ __forceinline__ bool continue_path(const DScene& sc, const lumo_material& m, const DHit& ho, V3 wo, V3 wi,
+                                              const double* delta, PathReg& P, Ray& rn) {
+    rn = spawn(ho, wi);
+    const double p_scatter = bsdf_pdf<FX>(sc, m, ho, wo, rn.d, P.L);
+    bool alive = false;
+    if (!(p_scatter <= 0.0)) {  // path_trace.rs:47: a NaN pdf continues the path
+        const DColor bsdf = bsdf_f<FX>(sc, m, ho, wo, rn.d, P.L);
+        P.g = P.g * (bsdf * shading_cosine(m, rn.d, ho.ns) / p_scatter);
+        alive = true;
+        if ((int)P.depth >= RR_DEPTH) {
+            const double lum = luminance(sc, P.g, P.L);
+            const double rr_prob = rmin(lum / delta[P.task], 1.0);
+            if (xs_float(P.rng) > rr_prob)
+                alive = false;
+            else
+                P.g = P.g / rr_prob;
+        }
+    }
+    P.flags = mat_is_specular<FX>(m) ? QF_SPECULAR : 0u;
+    return alive;
+}
+
 // Scene::hit (scene.rs:119-147) of every queued ray.  LDS: 0 scene in HBM, 1 whole scene staged
 // in LDS (small scenes), 2 TOP staging (the BVHs' top levels and the object records in LDS,
 // TOP_BLOCK threads per block: one block fills a CU).
@@ -191,6 +281,9 @@ __device__ __forceinline__ uint32_t block_by_material(const DScene& sc, const Hi
 // per slot (the radiance after k_shadow_q when the path still has shadow rays pending).
 // SPLIT (n_shadow > 1): the path's hit record and RNG state go to its NEE header and k_nee_gen
 // generates the pairs, one thread each; this kernel steps its RNG past their draws.
+// The bounce is written out here, not composed of load_path / sample_step / continue_path /
+// store_next: composed, with the same operations per path, the C2 frame measured 3 % slower
+// (DESIGN.md 4 "One bounce", profiles/r08).
 template <int FX, bool SPLIT>
 __global__ __launch_bounds__(BLOCK, FX == 0 ? LUMO_SHADE_WAVES_LEAN : LUMO_SHADE_WAVES) void k_shade_q(DScene sc, Paths S, Tasks T, QState cur, QState nxt,
                                                                       uint32_t skip_below) {
@@ -335,52 +428,67 @@ __global__ __launch_bounds__(BLOCK, FX == 0 ? LUMO_SHADE_WAVES_LEAN : LUMO_SHADE
     }
 }
 
-// the record's ray (planes b .. b + 5)
-__device__ __forceinline__ RayX shadow_ray(const ShadowQ& Q, int b, size_t r) {
-    return rayx(Ray{V3{Q.D(b, r), Q.D(b + 1, r), Q.D(b + 2, r)}, V3{Q.D(b + 3, r), Q.D(b + 4, r), Q.D(b + 5, r)}});
-}
-// mis_sample (integrator.rs:139-184) of a record whose light hit hi is visible
-template <int FX>
-__device__ __forceinline__ DColor shadow_mis(const DScene& sc, const ShadowQ& Q, int b, size_t r, bool li_mode,
-                                             uint32_t p, const RayX& ri, int li, const DHit& hi) {
+// Where a NEE record waits for its visibility walk.  Each form gives the record's ray and bsdf_pdf
+// (needed before the walk) and, for mis_sample after a visible hit, its bsdf_f, shading cosine and
+// the path's wavelengths; what a form reads from memory it reads when asked, so that it holds no
+// registers across the walk.
+// RecQ: the ShadowQ planes at base b (L: SD_LO, B: SD_BO) of pair r, the wavelengths in header p.
+struct RecQ {
+    const ShadowQ& Q;
+    int b;
+    size_t r;
+    uint32_t p;
+    __device__ __forceinline__ Ray ray() const {
+        return Ray{V3{Q.D(b, r), Q.D(b + 1, r), Q.D(b + 2, r)}, V3{Q.D(b + 3, r), Q.D(b + 4, r), Q.D(b + 5, r)}};
+    }
+    __device__ __forceinline__ double pdf() const { return Q.D(b + 10, r); }
+    __device__ __forceinline__ DColor f() const { return DColor{{Q.D(b + 6, r), Q.D(b + 7, r), Q.D(b + 8, r), Q.D(b + 9, r)}}; }
+    __device__ __forceinline__ double cosv() const { return Q.D(b + 11, r); }
+    __device__ __forceinline__ void lam(double* L) const {
+        for (int k = 0; k < NS; ++k) L[k] = Q.HD(SH_L + k, p);
+    }
+};
+
+// mis_sample (integrator.rs:139-184) of record R whose light hit hi along ri is visible
+template <int FX, class Rec>
+__device__ __forceinline__ DColor mis_sample(const DScene& sc, const Rec& R, int li, bool li_mode, const RayX& ri,
+                                             const DHit& hi) {
     DColor out = cfill(0.0);
     const lumo_object& Lo = sc.lights[li];
     const double p_lig = light_pdf<FX>(sc, Lo, ri, hi.p, hi.ng);
-    const double p_sct = Q.D(b + 10, r);
+    const double p_sct = R.pdf();
     if (!(p_lig == 0.0 || p_sct == 0.0)) {
         double L[NS];
-        for (int k = 0; k < NS; ++k) L[k] = Q.HD(SH_L + k, p);
+        R.lam(L);
         const double denom = p_lig * p_lig + p_sct * p_sct;
         const double weight = li_mode ? (p_lig * p_lig) / denom : (p_sct * p_sct) / denom;
         const double p_denom = li_mode ? p_lig : p_sct;
         const lumo_material hm = sc.mats[hi.material];
-        const DColor f{{Q.D(b + 6, r), Q.D(b + 7, r), Q.D(b + 8, r), Q.D(b + 9, r)}};
-        out = f * cfill(1.0) * emit<FX>(sc, hm, L, hi.backface, hi.uv) * Q.D(b + 11, r) * weight / p_denom;
+        const DColor f = R.f();
+        out = f * cfill(1.0) * emit<FX>(sc, hm, L, hi.backface, hi.uv) * R.cosv() * weight / p_denom;
     }
     return out;
 }
 
-// Scene::hit_light + mis_sample of one NEE record (integrator.rs:100-184); plane base b.  The
-// path's wavelengths (header p) are read only after a visible hit, so they are not live across
-// the traversal.
-template <int STK, int FX, bool TOP = false>
-__device__ __forceinline__ DColor shadow_record_q(const DScene& sc, const ShadowQ& Q, int b, size_t r, bool li_mode,
-                                                  uint32_t p, Counters& C, bool* visible = nullptr) {
+// Scene::hit_light + mis_sample of one NEE record (integrator.rs:100-184) towards light li; RM: the
+// walk's reuse mode (dscene.h).
+template <int STK, int FX, bool TOP, int RM, class Rec>
+__device__ __forceinline__ DColor shadow_record(const DScene& sc, const Rec& R, int li, bool li_mode, Counters& C,
+                                                bool* visible = nullptr) {
 #if LUMO_SKIP_DEAD
     // integrator.rs:146: mis_sample returns 0 when p_sct == 0, before the hit is used, so the
     // record contributes 0 whether or not the light is visible: no traversal.
-    if (Q.D(b + 10, r) == 0.0) {
+    if (R.pdf() == 0.0) {
         C.resolved++;
         return cfill(0.0);
     }
 #endif
-    const RayX ri = shadow_ray(Q, b, r);
-    const int li = Q.I(SI_LIGHT, r);
+    const RayX ri = rayx(R.ray());
     DHit hi;
     DColor out = cfill(0.0);
-    if (scene_hit_light<STK, FX, TOP>(sc, ri, li, hi, C)) {
+    if (scene_hit_light<STK, FX, TOP, RM>(sc, ri, li, hi, C)) {
         if (visible) *visible = true;
-        out = shadow_mis<FX>(sc, Q, b, r, li_mode, p, ri, li, hi);
+        out = mis_sample<FX>(sc, R, li, li_mode, ri, hi);
     }
     return out;
 }
@@ -432,7 +540,7 @@ __global__ __launch_bounds__(LDS == 2 ? TOP_BLOCK : BLOCK, LUMO_SHADOW_WAVES) vo
             const size_t r = (size_t)(qv >> 1);
             const int which = qv & 1;  // 0: light-sampled record, 1: BSDF-sampled
             const int b = which ? SD_BO : SD_LO;
-            const DColor x = shadow_record_q<STK, FX, LDS == 2>(sc, Q, b, r, which == 0, (uint32_t)(r % Q.hcap), C);
+            const DColor x = shadow_record<STK, FX, LDS == 2, 0>(sc, RecQ{Q, b, r, (uint32_t)(r % Q.hcap)}, Q.I(SI_LIGHT, r), which == 0, C);
             for (int k = 0; k < NS; ++k) Q.D(b + 6 + k, r) = x.s[k];
         }
         flush_counters(C, S.tcount + TC_N);
@@ -461,7 +569,8 @@ __global__ __launch_bounds__(LDS == 2 ? TOP_BLOCK : BLOCK, LUMO_SHADOW_WAVES) vo
             if (rec == 1 && !Q.I(SI_BVALID, r)) break;
             const uint32_t c0 = C.aabb + C.kd + C.tri, a0 = C.aabb;
             bool vis = false;
-            const DColor x = shadow_record_q<STK, FX, LDS == 2>(sc, Q, rec ? SD_BO : SD_LO, r, rec == 0, p, C, &vis);
+            const DColor x = shadow_record<STK, FX, LDS == 2, 0>(sc, RecQ{Q, rec ? SD_BO : SD_LO, r, p}, Q.I(SI_LIGHT, r), rec == 0, C,
+                                                                       &vis);
             if (rec) b = x; else a = x;
             const uint32_t cost = C.aabb + C.kd + C.tri - c0;
             pc += cost;
@@ -486,8 +595,10 @@ __global__ __launch_bounds__(LDS == 2 ? TOP_BLOCK : BLOCK, LUMO_SHADOW_WAVES) vo
             }
         }
 #else
-        const DColor a = shadow_record_q<STK, FX, LDS == 2>(sc, Q, SD_LO, r, true, p, C);
-        const DColor b = Q.I(SI_BVALID, r) ? shadow_record_q<STK, FX, LDS == 2>(sc, Q, SD_BO, r, false, p, C) : cfill(0.0);
+        const DColor a = shadow_record<STK, FX, LDS == 2, 0>(sc, RecQ{Q, SD_LO, r, p}, Q.I(SI_LIGHT, r), true, C);
+        const DColor b = Q.I(SI_BVALID, r)
+                             ? shadow_record<STK, FX, LDS == 2, 0>(sc, RecQ{Q, SD_BO, r, p}, Q.I(SI_LIGHT, r), false, C)
+                             : cfill(0.0);
 #endif
         const DColor single = (cfill(0.0) + a + b) / Q.D(SD_PDFL, r);
         const DColor g{{Q.HD(SH_G, p), Q.HD(SH_G + 1, p), Q.HD(SH_G + 2, p), Q.HD(SH_G + 3, p)}};
@@ -637,38 +748,44 @@ __device__ __forceinline__ NeeRec nee_record(const DScene& sc, const lumo_materi
     return NeeRec{spawn(ho, w), record_f<FX>(sc, m, ho, wo, w, L, pdf), pdf, shading_cosine(m, w, ho.ns)};
 }
 
-// shadow_record_q on a record held in registers (Scene::hit_light + mis_sample,
-// integrator.rs:100-184); L is the path's wavelengths after the pair was generated.
-template <int STK, int FX>
-__device__ __forceinline__ DColor shadow_record_r(const DScene& sc, const NeeRec& R, int li, bool li_mode,
-                                                  const double* L, Counters& C) {
-#if LUMO_SKIP_DEAD
-    if (R.pdf == 0.0) {  // integrator.rs:146: p_sct == 0 contributes 0 whatever the visibility
-        C.resolved++;
-        return cfill(0.0);
-    }
-#endif
-    const RayX ri = rayx(R.ray);
-    DHit hi;
-    DColor out = cfill(0.0);
-    if (scene_hit_light<STK, FX, false, RM_BOUNCE<FX>>(sc, ri, li, hi, C)) {
-        const lumo_object& Lo = sc.lights[li];
-        const double p_lig = light_pdf<FX>(sc, Lo, ri, hi.p, hi.ng);
-        const double p_sct = R.pdf;
-        if (!(p_lig == 0.0 || p_sct == 0.0)) {
-            const double denom = p_lig * p_lig + p_sct * p_sct;
-            const double weight = li_mode ? (p_lig * p_lig) / denom : (p_sct * p_sct) / denom;
-            const double p_denom = li_mode ? p_lig : p_sct;
-            const lumo_material hm = sc.mats[hi.material];
-            out = R.f * cfill(1.0) * emit<FX>(sc, hm, L, hi.backface, hi.uv) * R.cosv * weight / p_denom;
-        }
-    }
-    return out;
+// The light pick and the L record of a NEE pair (integrator.rs:87-110; 3 draws), then its B record
+// (integrator.rs:111-137; 3 draws, the sample may terminate wavelengths of P.L): nee_pair's two
+// halves for the kernels that keep the records out of HBM.
+template <int FX>
+__device__ __forceinline__ NeeRec nee_light_record(const DScene& sc, const lumo_material& m, const DHit& ho, V3 wo,
+                                                   PathReg& P, int& li) {
+    li = sample_light(sc, xs_float(P.rng));
+    const V2 rs = xs_vec2(P.rng);
+    return nee_record<FX>(sc, m, ho, wo, light_sample_towards<FX>(sc, sc.lights[li], ho.p, rs), P.L);
+}
+template <int FX>
+__device__ __forceinline__ bool nee_bsdf_record(const DScene& sc, const lumo_material& m, const DHit& ho, V3 wo,
+                                                PathReg& P, NeeRec& RB) {
+    const double ru = xs_float(P.rng);
+    const V2 rsq = xs_vec2(P.rng);
+    V3 wb;
+    const bool ok = bsdf_sample<FX>(sc, m, ho, wo, P.L, ru, rsq, wb);
+    if (ok) RB = nee_record<FX>(sc, m, ho, wo, wb, P.L);
+    return ok;
 }
 
-// shadow_record_r with the record's bsdf_f and shading cosine read from LDS only after the
-// traversal (`fc`: f[0..3] at fc[0], fc[nt], fc[2nt], fc[3nt], the cosine at fc[cos_at * nt]), so
-// they hold no registers during the walk.  Same operations in the same order.
+// A record held in registers (the tail); L: the path's wavelengths after the pair was generated.
+struct RecReg {
+    const NeeRec& R;
+    const double* L;
+    __device__ __forceinline__ Ray ray() const { return R.ray; }
+    __device__ __forceinline__ double pdf() const { return R.pdf; }
+    __device__ __forceinline__ DColor f() const { return R.f; }
+    __device__ __forceinline__ double cosv() const { return R.cosv; }
+    __device__ __forceinline__ void lam(double* o) const {
+        for (int k = 0; k < NS; ++k) o[k] = L[k];
+    }
+};
+// shadow_record and mis_sample of the fused kernel's records, whose bsdf_f and shading cosine are
+// read from LDS only after the traversal (`fc`: f[0..3] at fc[0], fc[nt], fc[2nt], fc[3nt], the cosine
+// at fc[cos_at * nt]), so they hold no registers during the walk.  Written out, like that kernel's
+// hit record, NEE pair and continuation: the full-feature k_bounce_q<4, true, 1, false> went from 184
+// to 337 - 509 spilled VGPRs with any of them behind a shared helper (profiles/r08).
 template <int STK, int FX>
 __device__ __forceinline__ DColor shadow_record_lds(const DScene& sc, const Ray& ray, double pdf, const double* fc,
                                                     int cos_at, uint32_t nt, int li, bool li_mode, const double* L,
@@ -698,21 +815,19 @@ __device__ __forceinline__ DColor shadow_record_lds(const DScene& sc, const Ray&
     return out;
 }
 
-#ifndef LUMO_PARK_NEE
-#define LUMO_PARK_NEE 1
-#endif
 // doubles per thread in k_bounce_q's LDS: the B record (12), the L record's f and cosine and g_nee (9)
-constexpr int PARK_DOUBLES = LUMO_PARK_NEE ? 12 + 9 : 12;
+constexpr int PARK_DOUBLES = 12 + 9;
 
-// A path between bounces, in registers (one QState entry).
-struct PathReg {
-    Ray ro;
-    DColor g, rad;
-    double L[NS];
-    Xorshift rng;
-    int32_t slot, task;
-    uint32_t depth, flags, queries;
-};
+// The record of a closest hit found by this thread's own walk: from the accepted test's e / det
+// where the walk kept them, else the GEO test again (the wide walks keep none).
+template <int STK, int FX>
+__device__ __forceinline__ void walk_hit_record(const DScene& sc, const HitRef& hr, const TriAcc& acc, const Ray& ro,
+                                                DHit& ho) {
+    if constexpr (STK == 0 || RM_BOUNCE<FX> != 2)
+        hit_record<FX>(sc, hr, rayx(ro), ho);
+    else
+        hit_record_acc<FX>(sc, hr, acc, ro, ho);
+}
 
 // One bounce of one path with n_shadow == 1 (path_trace.rs:18-77, integrator.rs:74-184).
 // Returns whether the path continues; P then holds the next bounce's ray, throughput, flags and
@@ -722,26 +837,18 @@ struct PathReg {
 template <int STK, int FX>
 __device__ __forceinline__ bool bounce_path(const DScene& sc, const double* delta, PathReg& P, Counters& Cc,
                                             Counters& Cs) {
-    const RayX rx = rayx(P.ro);
     TriAcc acc{V3{0.0, 0.0, 0.0}, 0.0};
-    const HitRef hr = scene_hit<STK, FX, false, false, RM_BOUNCE<FX>>(sc, rx, Cc, acc);  // Scene::hit (k_closest_q)
+    const HitRef hr = scene_hit<STK, FX, false, false, RM_BOUNCE<FX>>(sc, rayx(P.ro), Cc, acc);  // Scene::hit (k_closest_q)
     P.queries += 1u;
     if (hr.kind == 0) return false;
     DHit ho;
-    if constexpr (STK == 0 || RM_BOUNCE<FX> != 2)  // the wide walks keep no e / det: the GEO test again
-        hit_record<FX>(sc, hr, rx, ho);
-    else
-        hit_record_acc<FX>(sc, hr, acc, P.ro, ho);
+    walk_hit_record<STK, FX>(sc, hr, acc, P.ro, ho);
     const lumo_material m = sc.mats[ho.material];
     const V3 wo = -P.ro.d;
-    const double rand_u = xs_float(P.rng);
-    const V2 rsq = xs_vec2(P.rng);
     V3 wi;
-    if (!bsdf_sample<FX>(sc, m, ho, wo, P.L, rand_u, rsq, wi)) {  // may terminate L
-        if (P.flags & QF_SPECULAR) P.rad = P.rad + P.g * emit<FX>(sc, m, P.L, ho.backface, ho.uv);
-        return false;
-    }
-    const bool resolve = !mat_is_delta<FX>(sc, m, P.L);
+    const int st = sample_step<FX>(sc, m, ho, wo, P, wi);
+    if (st == 0) return false;
+    const bool resolve = st == 2;
     // the NEE pair (nee_pair): both records generated first, traced after the continuation, so
     // the hit record and material are dead during the traversals (the traversals draw nothing,
     // so the RNG sequence is lumo's: BSDF sample, light pick + direction, BSDF sample, RR)
@@ -751,41 +858,20 @@ __device__ __forceinline__ bool bounce_path(const DScene& sc, const double* delt
     bool ok = false;
     const DColor g_nee = P.g;
     if (resolve) {
-        li = sample_light(sc, xs_float(P.rng));
+        RL = nee_light_record<FX>(sc, m, ho, wo, P, li);
         pdf_light = sc.alias_pdf[li];
-        const V2 rs = xs_vec2(P.rng);
-        RL = nee_record<FX>(sc, m, ho, wo, light_sample_towards<FX>(sc, sc.lights[li], ho.p, rs), P.L);
-        const double ru = xs_float(P.rng);
-        const V2 rsq2 = xs_vec2(P.rng);
-        V3 wb;
-        ok = bsdf_sample<FX>(sc, m, ho, wo, P.L, ru, rsq2, wb);  // may terminate L
-        if (ok) RB = nee_record<FX>(sc, m, ho, wo, wb, P.L);
+        ok = nee_bsdf_record<FX>(sc, m, ho, wo, P, RB);
         P.queries += 1u + (ok ? 1u : 0u);
     }
-    // continuation (path_trace.rs:42-77)
-    const Ray rn = spawn(ho, wi);
-    const double p_scatter = bsdf_pdf<FX>(sc, m, ho, wo, rn.d, P.L);
-    bool alive = false;
-    if (!(p_scatter <= 0.0)) {  // path_trace.rs:47: a NaN pdf continues the path
-        const DColor bsdf = bsdf_f<FX>(sc, m, ho, wo, rn.d, P.L);
-        P.g = P.g * (bsdf * shading_cosine(m, rn.d, ho.ns) / p_scatter);
-        alive = true;
-        if ((int)P.depth >= RR_DEPTH) {
-            const double lum = luminance(sc, P.g, P.L);
-            const double rr_prob = rmin(lum / delta[P.task], 1.0);
-            if (xs_float(P.rng) > rr_prob)
-                alive = false;
-            else
-                P.g = P.g / rr_prob;
-        }
-    }
+    Ray rn;
+    const bool alive = continue_path<FX>(sc, m, ho, wo, wi, delta, P, rn);
     if (resolve) {  // k_shadow_q (NS1): single = (0 + L-record + B-record) / pdf_light
         // one inlined traversal for both records (selects, not an indexed array: no scratch)
         DColor a = cfill(0.0), b = cfill(0.0);
 #pragma unroll 1
         for (int k = 0; k < (ok ? 2 : 1); ++k) {
             const NeeRec Rk = k == 0 ? RL : RB;
-            const DColor x = shadow_record_r<STK, FX>(sc, Rk, li, k == 0, P.L, Cs);
+            const DColor x = shadow_record<STK, FX, false, RM_BOUNCE<FX>>(sc, RecReg{Rk, P.L}, li, k == 0, Cs);
             if (k == 0)
                 a = x;
             else
@@ -796,32 +882,9 @@ __device__ __forceinline__ bool bounce_path(const DScene& sc, const double* delt
     }
     if (alive) {
         P.ro = rn;
-        P.flags = mat_is_specular<FX>(m) ? QF_SPECULAR : 0u;
         P.depth += 1u;
     }
     return alive;
-}
-
-__device__ __forceinline__ PathReg load_path(const QState& cur, uint32_t q) {
-    PathReg P;
-    P.slot = cur.I(QI_SLOT, q);
-    P.task = cur.I(QI_TASK, q);
-    P.depth = (uint32_t)cur.I(QI_DEPTH, q);
-    P.flags = (uint32_t)cur.I(QI_FLAGS, q);
-    P.queries = (uint32_t)cur.I(QI_QUERIES, q);
-    P.ro = Ray{qv3(cur, QD_O, q), qv3(cur, QD_D, q)};
-    P.g = qc(cur, QD_G, q);
-    P.rad = qc(cur, QD_R, q);
-    if (P.flags & QF_PENDING) P.rad = P.rad + qc(cur, QD_P, q);  // the previous bounce's NEE term
-    for (int i = 0; i < NS; ++i) P.L[i] = cur.D(QD_L + i, q);
-    P.rng = Xorshift{cur.R(0, q), cur.R(1, q)};
-    return P;
-}
-__device__ __forceinline__ void store_final(const Paths& S, const PathReg& P) {  // FilmSample (path_trace.rs:79-81)
-    for (int i = 0; i < NS; ++i) S.lam[4 * P.slot + i] = P.L[i];
-    S.depth[P.slot] = P.depth;
-    S.queries[P.slot] = P.queries;
-    stc(S.rad, P.slot, P.rad);
 }
 
 // TAIL = true: launched ahead of every bounce of an n_shadow == 1 pass; when fewer than
@@ -834,29 +897,10 @@ __device__ __forceinline__ void store_final(const Paths& S, const PathReg& P) { 
 // final radiance (as k_shadow_q).  Neither hits nor records go through HBM.
 // The pipeline's merged passes run their tails pass by pass (each needs its previous pass's ring
 // for Russian roulette): k_split_passes first cuts the unit's queue into one segment per pass.
-// LUMO_BOUNCE_ARGPTR = 1: the arguments through the per-stream BounceArgs block (state.h).  It
-// took k_bounce_q<4, true, 0, false> from 170 to 43 spilled SGPRs (VGPR spills 29 and scratch 112 B
-// unchanged) but not the frame: C1 64-spp 168-172 ms by value, 172-177 ms by pointer; 1/8 share
-// 309-314 / 308-311 ms.  Off by default.
-#ifndef LUMO_BOUNCE_ARGPTR
-#define LUMO_BOUNCE_ARGPTR 0
-#endif
-template <int STK>
-__global__ void k_put_args(BounceArgs a, BounceArgs* out) {
-    if (threadIdx.x == 0) *out = a;
-}
 template <int STK, bool LDS, int FX, bool TAIL>
-__global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_q(
-#if LUMO_BOUNCE_ARGPTR
-    const BounceArgs* __restrict__ A, uint32_t tail_below, int dyn) {
-    const DScene& sc0 = A->sc;
-    const Paths& S = A->S;
-    const Tasks& T = A->T;
-    const QState& cur = A->cur;
-    const QState& nxt = A->nxt;
-#else
-    DScene sc0, Paths S, Tasks T, QState cur, QState nxt, uint32_t tail_below, int dyn) {
-#endif
+__global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_q(DScene sc0, Paths S, Tasks T, QState cur,
+                                                                                 QState nxt, uint32_t tail_below,
+                                                                                 int dyn) {
     extern __shared__ __attribute__((aligned(16))) char lds_scene[];
     const uint32_t count = S.counts[CNT_CUR];
     if ((count < tail_below) != TAIL) return;      // the other kernel takes this bounce
@@ -911,7 +955,6 @@ __global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_
             bool resolve = false, alive = false, ok = false;
             NeeRec RL;
             int li = 0;
-            double pdf_light = 1.0;
             DColor g_nee = cfill(0.0);
             Ray rn{V3{0, 0, 0}, V3{0, 0, 0}};
             if (live) {
@@ -925,26 +968,21 @@ __global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_
                         hit_record_acc<FX>(sc, hr, hacc, P.ro, ho);
                     const lumo_material m = sc.mats[ho.material];
                     const V3 wo = -P.ro.d;
-                    const double rand_u = xs_float(P.rng);
-                    const V2 rsq = xs_vec2(P.rng);
                     V3 wi;
-                    if (!bsdf_sample<FX>(sc, m, ho, wo, P.L, rand_u, rsq, wi)) {  // may terminate L
-                        if (P.flags & QF_SPECULAR) P.rad = P.rad + P.g * emit<FX>(sc, m, P.L, ho.backface, ho.uv);
-                    } else {
-                        resolve = !mat_is_delta<FX>(sc, m, P.L);
+                    const int st = sample_step<FX>(sc, m, ho, wo, P, wi);
+                    if (st != 0) {
+                        resolve = st == 2;
                         g_nee = P.g;
                         if (resolve) {  // nee_pair
                             li = sample_light(sc, xs_float(P.rng));
-                            pdf_light = sc.alias_pdf[li];
                             const V2 rs = xs_vec2(P.rng);
                             RL = nee_record<FX>(sc, m, ho, wo, light_sample_towards<FX>(sc, sc.lights[li], ho.p, rs),
                                                 P.L);
-                            if (LUMO_PARK_NEE) {  // the L record's f / cosine and g_nee wait in LDS
-                                double* rl = rb_lds + 12 * nt + threadIdx.x;
-                                for (int k = 0; k < 4; ++k) rl[k * nt] = RL.f.s[k];
-                                rl[4 * nt] = RL.cosv;
-                                for (int k = 0; k < 4; ++k) rl[(5 + k) * nt] = g_nee.s[k];
-                            }
+                            // the L record's f / cosine and g_nee wait in LDS
+                            double* rl = rb_lds + 12 * nt + threadIdx.x;
+                            for (int k = 0; k < 4; ++k) rl[k * nt] = RL.f.s[k];
+                            rl[4 * nt] = RL.cosv;
+                            for (int k = 0; k < 4; ++k) rl[(5 + k) * nt] = g_nee.s[k];
                             const double ru = xs_float(P.rng);
                             const V2 rsq2 = xs_vec2(P.rng);
                             V3 wb;
@@ -987,25 +1025,10 @@ __global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_
             const uint32_t np = dyn ? block_slot_fetch(alive, S.counts + CNT_NEXT, S.counts + CNT_FETCH_B, &next_base)
                                     : block_slot(alive, S.counts + CNT_NEXT);
             LUMO_PHASE(5);
-            if (alive) {
-                qv3(nxt, QD_O, np, rn.o);
-                qv3(nxt, QD_D, np, rn.d);
-                qc(nxt, QD_G, np, P.g);
-                qc(nxt, QD_R, np, P.rad);
-                for (int i = 0; i < NS; ++i) nxt.D(QD_L + i, np) = P.L[i];
-                nxt.R(0, np) = P.rng.hi;
-                nxt.R(1, np) = P.rng.lo;
-                nxt.I(QI_SLOT, np) = P.slot;
-                nxt.I(QI_TASK, np) = P.task;
-                nxt.I(QI_DEPTH, np) = (int32_t)(P.depth + 1u);
-                nxt.I(QI_FLAGS, np) = (int32_t)(P.flags | (resolve ? (uint32_t)QF_PENDING : 0u));
-                nxt.I(QI_QUERIES, np) = (int32_t)P.queries;
-            } else if (live) {  // the path ends here (its radiance gains the NEE term below)
-                for (int i = 0; i < NS; ++i) S.lam[4 * P.slot + i] = P.L[i];
-                S.depth[P.slot] = P.depth;
-                S.queries[P.slot] = P.queries;
-                stc(S.rad, P.slot, P.rad);
-            }
+            if (alive)
+                store_next(nxt, np, P, rn, resolve);
+            else if (live)  // the path ends here (its radiance gains the NEE term below)
+                store_final(S, P);
             LUMO_PHASE(4);
 #if LUMO_PHASE_CLOCKS
             lanes[0] += 1;
@@ -1015,7 +1038,6 @@ __global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_
 #endif
             // phase 3: the pair's visibility + MIS (k_shadow_q, NS1)
             if (resolve) {
-#if LUMO_PARK_NEE
                 const double* rl = rb_lds + 12 * nt + threadIdx.x;
                 const DColor a = shadow_record_lds<STK, FX>(sc, RL.ray, RL.pdf, rl, 4, nt, li, true, P.L, Cs);
                 DColor b = cfill(0.0);
@@ -1028,21 +1050,6 @@ __global__ __launch_bounds__(BLOCK, TAIL ? 2 : LUMO_BOUNCE_WAVES) void k_bounce_
                 const DColor g_n{{rl[5 * nt], rl[6 * nt], rl[7 * nt], rl[8 * nt]}};
                 const DColor single = (cfill(0.0) + a + b) / pdf_l;
                 const DColor X = (cfill(0.0) + g_n * single) / 1.0;
-#else
-                const DColor a = shadow_record_r<STK, FX>(sc, RL, li, true, P.L, Cs);
-                DColor b = cfill(0.0);
-                if (ok) {
-                    NeeRec RB;
-                    const double* v = rb_lds + threadIdx.x;
-                    RB.ray = Ray{V3{v[0], v[nt], v[2 * nt]}, V3{v[3 * nt], v[4 * nt], v[5 * nt]}};
-                    RB.f = DColor{{v[6 * nt], v[7 * nt], v[8 * nt], v[9 * nt]}};
-                    RB.pdf = v[10 * nt];
-                    RB.cosv = v[11 * nt];
-                    b = shadow_record_r<STK, FX>(sc, RB, li, false, P.L, Cs);
-                }
-                const DColor single = (cfill(0.0) + a + b) / pdf_light;
-                const DColor X = (cfill(0.0) + g_nee * single) / 1.0;
-#endif
                 if (alive)
                     qc(nxt, QD_P, np, X);
                 else  // the radiance stored above, re-read by the thread that wrote it

@@ -38,3 +38,28 @@ def oracle_threads():
     except (OSError, ValueError):
         pass
     return max(1, min(n, 32))
+
+
+# The path-tracing kernel forms of an n_shadow == 1 scene, each chosen by the options alone (plain
+# pass loop, pipeline 0): the fused bounce, the tail kernel from the first bounce (tail_below above
+# the path count) and the split closest / shade / shadow kernels; "default" is the caller's device.
+SCHEDULES = [("default", None, None), ("fused", 1, 0), ("tail", 1, 1 << 30), ("split", 0, 0)]
+SCHEDULE_IDS = [s[0] for s in SCHEDULES]
+
+
+def render_scheduled(dev, scene, cam, tasks, how, fused, tail):
+    """render_tasks through schedule `how` (default: on dev), asserting that the kernel the case
+    names ran: n_shadow == 1, the schedule's fused flag, tail queries only in the tail form."""
+    import lumo_amd as L
+    d = dev if how == "default" else L.Device(0, fused=fused, tail_below=tail, pipeline=0)
+    try:
+        d.upload(scene, cam)
+        bufs, res = d.render_tasks(tasks)
+        if how != "default":
+            assert d.scene_info().n_shadow == 1
+            assert d.last_schedule().fused == fused
+            assert (d.stats().tail_queries > 0) == (how == "tail")
+    finally:
+        if d is not dev:
+            d.close()
+    return bufs, res

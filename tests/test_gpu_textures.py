@@ -9,7 +9,7 @@ import pytest
 import lumo_amd as L
 import oracle_ffi as O
 from lumo_amd import _ffi
-from parity import gpu_paths
+from parity import SCHEDULE_IDS, SCHEDULES, gpu_paths, oracle_threads, render_scheduled
 from scenes import default_camera, texture_zoo, textured_obj_zip
 
 pytestmark = pytest.mark.gpu
@@ -43,12 +43,18 @@ def test_texture_zoo_paths(dev, zoo, tile):
     _cmp(gpu_paths(dev, task), O.trace_paths(zoo.desc(), cam.desc, task))
 
 
-def test_texture_zoo_tiles(dev, zoo):
+@pytest.fixture(scope="module")
+def zoo_tiles(zoo):
     cam = default_camera((64, 48))
-    dev.upload(zoo, cam)
     tasks = L.make_tasks(64, 48, 16, SEED)
-    bufs, res = dev.render_tasks(tasks)
-    obufs, ores, _ = O.render_tasks(zoo.desc(), cam.desc, tasks, O.WAVEFRONT, 16)
+    obufs, ores, _ = O.render_tasks(zoo.desc(), cam.desc, tasks, O.WAVEFRONT, oracle_threads())
+    return cam, tasks, obufs, ores
+
+
+@pytest.mark.parametrize("how,fused,tail", SCHEDULES, ids=SCHEDULE_IDS)
+def test_texture_zoo_tiles(dev, zoo, zoo_tiles, how, fused, tail):
+    cam, tasks, obufs, ores = zoo_tiles
+    bufs, res = render_scheduled(dev, zoo, cam, tasks, how, fused, tail)
     for b, ob, r, orr in zip(bufs, obufs, res, ores):
         np.testing.assert_array_equal(b, ob)
         assert (r.num_rays, r.num_queries) == (orr.num_rays, orr.num_queries)

@@ -379,12 +379,12 @@ enum {
     LUMO_OPT_TOP_STAGING,      /* TOP staging of larger scenes: 0 / 1 (LUMO_TOP, 1)                    */
     LUMO_OPT_FUSED,            /* n_shadow = 1: -1 fused bounce when LDS-staged, 0 three kernels,
                                   1 fused (LUMO_FUSED, -1)                                          */
-    LUMO_OPT_TAIL_BELOW,       /* n_shadow = 1: tail kernel below this many live paths, 0 never
-                                  (LUMO_TAIL, 65536)                                               */
+    LUMO_OPT_TAIL_BELOW,       /* n_shadow = 1: tail kernel below this many live paths, 0 never,
+                                  0-2^31 (LUMO_TAIL, 65536)                                        */
     LUMO_OPT_PIPELINE,         /* passes overlapped: 0 off, fused bounces 1-3 head streams, split
                                   schedule on when > 0 (LUMO_PIPELINE, 3)                            */
-    LUMO_OPT_HEADS,            /* fused pipeline: bounces per pass on its head stream, 0 auto
-                                  (LUMO_HEADS, 0)                                                   */
+    LUMO_OPT_HEADS,            /* fused pipeline: bounces per pass on its head stream, 0 auto,
+                                  1-64 (LUMO_HEADS, 0)                                              */
     LUMO_OPT_MERGE_PASSES,     /* fused and split pipelines: consecutive passes whose cameras and
                                   head bounces (those before Russian roulette) run as one queue,
                                   0 auto, 1-8 (LUMO_MERGE, 0)                                        */
@@ -393,21 +393,26 @@ enum {
                                   (LUMO_BOUNCE_THREADS, 256)                                        */
     LUMO_OPT_SPLIT_PIPE,       /* split schedule: units in flight 1-4 (LUMO_SPLIT_PIPE, 4)           */
     LUMO_OPT_SPLIT_GROUPS,     /* split schedule: independent task groups 1-4 (LUMO_SPLIT_GROUPS, 2) */
-    LUMO_OPT_BDPT_TAIL,        /* BDPT: walk-tail kernel below this many live subpaths, 0 never
-                                  (LUMO_BDPT_TAIL, 65536)                                           */
-    LUMO_OPT_BOUNCE_AHEAD,     /* bounces enqueued ahead of the host's count snapshots 1-63
+    LUMO_OPT_BDPT_TAIL,        /* BDPT: walk-tail kernel below this many live subpaths, 0 never,
+                                  0-2^31 (LUMO_BDPT_TAIL, 65536)                                    */
+    LUMO_OPT_BOUNCE_AHEAD,     /* bounces enqueued ahead of the host's count snapshots 1-15 (the
+                                  pipelined schedules keep 16 snapshot slots per pass set)
                                   (LUMO_BOUNCE_AHEAD, 3)                                            */
-    LUMO_OPT_LDS_GRID,         /* grid cap of LDS-staged kernels (LUMO_LDS_GRID, 1.5 x CUs = 384)    */
-    LUMO_OPT_TOP_GRID,         /* grid cap of TOP kernels (LUMO_TOP_GRID, half the CU count = 128)   */
-    LUMO_OPT_TOP_KB,           /* upload: TOP set budget in KiB, <= the CU's LDS (LUMO_TOP_KB)       */
-    LUMO_OPT_KD_LDS,           /* upload: kd stack entries per thread in LDS in TOP kernels
+    LUMO_OPT_LDS_GRID,         /* grid cap of LDS-staged kernels, 1-2^20
+                                  (LUMO_LDS_GRID, 1.5 x CUs = 384)                                  */
+    LUMO_OPT_TOP_GRID,         /* grid cap of TOP kernels, 1-2^20
+                                  (LUMO_TOP_GRID, half the CU count = 128)                          */
+    LUMO_OPT_TOP_KB,           /* upload: TOP set budget in KiB, 0 to the CU's LDS (160 on MI355X)
+                                  (LUMO_TOP_KB, the CU's LDS)                                       */
+    LUMO_OPT_KD_LDS,           /* upload: kd stack entries per thread in LDS in TOP kernels, 0-64
                                   (LUMO_KD_LDS, 8)                                                  */
-    LUMO_OPT_STACK_CLASS,      /* upload: kd stack class override, 0 auto; never below the scene's
-                                  need (LUMO_STACK_CLASS, 0)                                        */
+    LUMO_OPT_STACK_CLASS,      /* upload: kd stack class override, 0 auto or one of 4 / 8 / 16 / 24 /
+                                  32 / 48 / 64; never below the scene's need (LUMO_STACK_CLASS, 0)  */
     LUMO_OPT_FULL_KERNELS,     /* upload: general feature kernels even for lean scenes: 0 / 1
                                   (LUMO_FULL_KERNELS, 0)                                            */
     LUMO_OPT_POISON,           /* debug: fill every newly allocated device buffer with 0xFF bytes,
-                                  so a read of a buffer before its first write shows (LUMO_POISON, 0)*/
+                                  so a read of a buffer before its first write shows: 0 / 1
+                                  (LUMO_POISON, 0)                                                  */
     LUMO_OPT_TAIL_PRIORITY,    /* fused pipeline: the stream of the passes' tails, films and rings (the
                                   chain each pass's Russian roulette waits on) at high priority: 0 / 1
                                   (LUMO_TAIL_PRIORITY, 0)                                           */

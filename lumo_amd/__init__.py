@@ -575,6 +575,12 @@ class Camera:
             self.p.color_space = int(cs)
             return self
 
+        def filter(self, radius, sigma):
+            """PixelFilter::Gaussian(radius, sigma) (filter.rs:20-24; default 1.5, 0.375).  The device
+            gathers over 3x3 pixels: it takes radii in (0.5, 1.5] and refuses others at upload."""
+            self.p.filter_radius, self.p.filter_sigma = float(radius), float(sigma)
+            return self
+
         def build(self):
             d = _ffi.CameraDesc()
             check(lib().lumo_camera_build(C.byref(self.p), C.byref(d)), "camera build")
@@ -920,7 +926,8 @@ class Renderer:
             chunks = (tasks_of_tiles(tasks, w, h, tiles) for tiles in queue)
         dev = Device(self._device)
         dev.upload(self.scene, self.camera)
-        film = Film(w, h, getattr(self.camera, "color_space", 1), samples=self._samples)
+        film = Film(w, h, getattr(self.camera, "color_space", 1), samples=self._samples,
+                    filter_radius=self.camera.desc.filter_radius, filter_sigma=self.camera.desc.filter_sigma)
         self.num_rays = self.num_camera_rays = 0
         self.tasks_rendered = 0
         for mine in chunks:

@@ -172,7 +172,8 @@ class ScheduleInfo(C.Structure):
 
 
 SCHED_SEQUENTIAL, SCHED_FUSED_PIPELINE, SCHED_SPLIT_PIPELINE = range(3)
-# LUMO_OPT_* (include/lumo_amd.h), by the name Device.set_option takes
+# LUMO_OPT_* (include/lumo_amd.h), by the name Device.set_option takes; the header gives each option's
+# range (bounce_ahead: 1-15)
 OPTIONS = ["timing", "lds_staging", "top_staging", "fused", "tail_below", "pipeline", "heads", "merge_passes",
            "dyn_fetch", "bounce_threads", "split_pipe", "split_groups", "bdpt_tail", "bounce_ahead", "lds_grid",
            "top_grid", "top_kb", "kd_lds", "stack_class", "full_kernels", "poison", "tail_priority", "top_kd",

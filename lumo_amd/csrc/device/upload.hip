@@ -538,6 +538,8 @@ lumo_status lumo_camera_set(void* ctx, const lumo_camera_desc* d) {
     if (!c || !d) return LUMO_ERR_INVALID;
     if (d->orthographic != 0 && d->orthographic != 1) return LUMO_ERR_INVALID;
     if (d->width <= 0 || d->height <= 0 || !(d->filter_radius > 0.0) || !(d->filter_sigma > 0.0)) return LUMO_ERR_INVALID;
+    // 3x3 gather footprint; refused before anything is written, so the context keeps its camera
+    if (!(d->filter_radius < 1e9) || (uint64_t)std::ceil(d->filter_radius - 0.5) != 1) return LUMO_ERR_UNSUPPORTED;
     auto get = [](const double (&a)[2][16]) {
         Xform x;
         M4* ms[2] = {&x.m, &x.inv};
@@ -571,7 +573,6 @@ lumo_status lumo_camera_set(void* ctx, const lumo_camera_desc* d) {
         const V2 pd = p_max - p_min;
         c->cam.image_plane_area = fabs(pd.x * pd.y);
     }
-    if ((uint64_t)std::ceil(d->filter_radius - 0.5) != 1) return LUMO_ERR_UNSUPPORTED;  // 3x3 gather footprint
     c->has_camera = true;
     return LUMO_OK;
 }

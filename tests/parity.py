@@ -25,6 +25,37 @@ def gpu_paths(dev, task, sampler=0):
                 delta=delta)
 
 
+def assert_paths_equal(g, o):
+    """Every per-path output of lumo_debug_paths and the pass deltas against the oracle's, bit for bit."""
+    for k in ("depth", "raster", "lam", "radiance", "delta"):
+        np.testing.assert_array_equal(g[k], o[k], err_msg=k)
+
+
+def assert_tiles_equal(bufs, res, obufs, ores, camera_rays=False):
+    """Every task's tile buffer bit-equal to the oracle's and its ray and query counts the same."""
+    assert len(bufs) == len(obufs)
+    for i, (b, ob, r, orr) in enumerate(zip(bufs, obufs, res, ores)):
+        np.testing.assert_array_equal(b, ob, err_msg=f"task {i}")
+        assert (r.num_rays, r.num_queries) == (orr.num_rays, orr.num_queries), f"task {i}"
+        if camera_rays:
+            assert r.num_camera_rays == orr.num_camera_rays, f"task {i}"
+
+
+def assert_splats_equal(sp, osp):
+    """Per-task light-tracing splat lists (lumo's order) bit-equal to the oracle's."""
+    assert len(sp) == len(osp)
+    for i, (s, os_) in enumerate(zip(sp, osp)):
+        assert len(s) == len(os_), f"task {i}"
+        for k in ("x", "y", "rgb"):
+            np.testing.assert_array_equal(s[k], os_[k], err_msg=f"task {i} {k}")
+
+
+def stage_launches(before, after, stage):
+    """Launches of a stage (a name of _ffi.STAGES) between two Device.stats() readings."""
+    k = _ffi.STAGES.index(stage)
+    return after.launches[k] - before.launches[k]
+
+
 def oracle_threads():
     """Threads for the CPU oracle in a parity test: the cores this process may use (the affinity
     mask, capped by a cgroup v2 quota: on the GPU box os.cpu_count() is the whole machine)."""

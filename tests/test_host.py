@@ -244,6 +244,17 @@ def test_camera_rejects_bad_params():
         L.Camera.builder().resolution((0, 10)).build()
 
 
+def test_camera_filter_setter():
+    """Camera.Builder.filter(radius, sigma) reaches the camera descriptor; the builder takes any
+    positive pair (the device narrows the radius to its 3x3 footprint at upload) and refuses others."""
+    cam = L.Camera.cornell_box_builder().resolution((40, 24)).filter(0.6, 3.0).build()
+    assert (cam.desc.filter_radius, cam.desc.filter_sigma) == (0.6, 3.0)
+    assert L.Camera.builder().filter(2.5, 0.1).build().desc.filter_radius == 2.5
+    for r, s in ((0.0, 0.375), (-1.0, 0.375), (float("nan"), 0.375), (1.5, 0.0), (1.5, float("nan"))):
+        with pytest.raises(RuntimeError, match="INVALID"):
+            L.Camera.builder().filter(r, s).build()
+
+
 def test_scene_without_light_fails():
     s = L.Scene()
     s.add_mesh(np.array(CUBE_V, dtype=float), CUBE_F, L.Material.lambertian(L.Spectrum.from_rgb(0.5, 0.5, 0.5)))

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../../include/lumo_amd.h"
+#include "../common/sched_plan.h"
 
 #define LUMO_MAIN_TU
 #include "launch.h"
@@ -791,31 +792,28 @@ __global__ __launch_bounds__(BLOCK) void k_calib_write8(double* __restrict__ out
 
 // ================================================================== host side
 
-// Merged passes of the fused pipeline (render_pipelined): at most MAX_MERGE (state.h) passes per
-// unit, by default as many as bring a unit to about kMergeTarget paths (a full 1024^2 frame: 1).
-constexpr uint64_t kMergeTarget = (uint64_t)1 << 21;
-
 int ceil_div(uint64_t a, uint64_t b) { return (int)((a + b - 1) / b); }
 
+// Buffers of a pass set (alloc_pass_set below): the per-pass outputs and counters, the ping-pong
+// queues, the closest hits and NEE records, the ray sorting buffers.
+enum SetField {
+    F_RAD, F_LAM, F_RASTER, F_DEPTH, F_QUERIES, F_P_VALID, F_COUNTS,
+    F_QS0_D, F_QS0_R, F_QS0_I, F_QS1_D, F_QS1_R, F_QS1_I,
+    F_HQ_T, F_HQ_I, F_SQ_D, F_SQ_I, F_SQ_HD, F_SQ_HI, F_SQ_HR, F_SQ_QL,
+    F_SORT_KEYS, F_SORT_ORDER, F_SORT_WS, F_SET_COUNT
+};
 // Work-buffer carve-out (one allocation per field, grown on demand)
 enum WorkId {
-    W_RO, W_RD, W_GATH, W_RAD, W_LAM, W_RASTER, W_RNG, W_DEPTH, W_FLAGS, W_QUERIES, W_TASK, W_PIX, W_PSEED, W_MJRNG,
-    W_MJSTATE, W_PERM, W_HIT_T, W_HIT_KIND, W_HIT_OBJ, W_HIT_TRI, W_SH_O, W_SH_D, W_SH_F, W_SH_PSCT, W_SH_COS,
-    W_SH_OUT, W_SH_LIGHT, W_SH_FLAGS, W_G_SH, W_PDF_L, W_P_RGB, W_P_VALID, W_FILM, W_Q0, W_Q1,
-    W_SQ, W_RQ, W_COUNTS, W_TCOUNT, W_TASKS, W_FIRST, W_RING_COST, W_RING_LUM, W_RING_PTR, W_DELTA, W_NUM_RAYS,
+    W_RO, W_RD, W_GATH, W_RNG, W_FLAGS, W_TASK, W_PIX, W_PSEED, W_MJRNG, W_MJSTATE, W_PERM,
+    W_HIT_T, W_HIT_KIND, W_HIT_OBJ, W_HIT_TRI, W_SH_O, W_SH_D, W_SH_LIGHT, W_P_RGB, W_FILM, W_Q0, W_Q1,
+    W_TCOUNT, W_TASKS, W_FIRST, W_RING_COST, W_RING_LUM, W_RING_PTR, W_DELTA, W_NUM_RAYS,
     W_TQUERIES, W_DUMP_RAD, W_DUMP_LAM, W_DUMP_RASTER, W_DUMP_DEPTH, W_DUMP_DELTA,
     W_BD_LD, W_BD_LI, W_BD_CD, W_BD_CI, W_BD_SP, W_BD_SPN, W_BD_OVF, W_BD_CNT, W_BD_OFF,
     W_BD_FILM, W_BD_REDO_INDEX, W_BD_NL, W_BD_NC, W_BD_NITEMS, W_BD_IOFF, W_BD_DRAWS, W_BD_OK, W_BD_ITOTAL, W_BD_PDF,
     W_BD_WDEPTH, W_BD_CAMO, W_BD_CAMD, W_BD_RNG0, W_BD_LAM0, W_BD_NB, W_BD_OFFB,
-    W_CHECKS, W_QS0_D, W_QS0_R, W_QS0_I, W_QS1_D, W_QS1_R, W_QS1_I, W_HQ_T, W_HQ_I, W_SQ_D, W_SQ_I,
-    W_SQ_HD, W_SQ_HI, W_SQ_HR, W_RAD2, W_LAM2, W_RASTER2, W_DEPTH2, W_QUERIES2, W_P_VALID2, W_COUNTS2, W_QS2_D,
-    W_QS2_R, W_QS2_I, W_QS3_D, W_QS3_R, W_QS3_I, W_RAD3, W_LAM3, W_RASTER3, W_DEPTH3, W_QUERIES3, W_P_VALID3,
-    W_COUNTS3, W_QS4_D, W_QS4_R, W_QS4_I, W_QS5_D, W_QS5_R, W_QS5_I, W_RAD4, W_LAM4, W_RASTER4, W_DEPTH4,
-    W_QUERIES4, W_P_VALID4, W_COUNTS4, W_QS6_D, W_QS6_R, W_QS6_I, W_QS7_D, W_QS7_R, W_QS7_I,
-    W_SQ_QL, W_BD_LM, W_BD_LMF, W_BD_CM, W_BD_CMF,
-    W_SPLIT_SET1,  // render_split_pipelined sets 1..3: hits + NEE records, 8 buffers each
-    W_SORT_SET0 = W_SPLIT_SET1 + 3 * 8,  // ray sorting of pass set k: keys, order, workspace
-    W_COUNT = W_SORT_SET0 + 4 * 3
+    W_CHECKS, W_BD_LM, W_BD_LMF, W_BD_CM, W_BD_CMF,
+    W_SET0,  // pass set k's field f: W_SET0 + k * F_SET_COUNT + f
+    W_COUNT = W_SET0 + 4 * F_SET_COUNT
 };
 
 template <typename T>
@@ -954,64 +952,87 @@ void launch_trav(Ctx& c, uint64_t count, F&& f, hipStream_t stream = nullptr, bo
     by_stack_class(c.sc.stack_class, [&](auto K) { f(K, l); });
 }
 
-// Per-pass copies of the per-slot outputs, queue counters and queue-order state for the pipelined
-// schedules (pass set k = 1..3; set 0 is the render's own Paths).
-const int kSetWork[3][13] = {{W_RAD2, W_LAM2, W_RASTER2, W_DEPTH2, W_QUERIES2, W_P_VALID2, W_COUNTS2, W_QS2_D, W_QS2_R,
-                              W_QS2_I, W_QS3_D, W_QS3_R, W_QS3_I},
-                             {W_RAD3, W_LAM3, W_RASTER3, W_DEPTH3, W_QUERIES3, W_P_VALID3, W_COUNTS3, W_QS4_D, W_QS4_R,
-                              W_QS4_I, W_QS5_D, W_QS5_R, W_QS5_I},
-                             {W_RAD4, W_LAM4, W_RASTER4, W_DEPTH4, W_QUERIES4, W_P_VALID4, W_COUNTS4, W_QS6_D, W_QS6_R,
-                              W_QS6_I, W_QS7_D, W_QS7_R, W_QS7_I}};
-void alloc_pass_set(Ctx& c, Paths& Q, int k, int N, lumo_status& st) {
-    const int* w = kSetWork[k - 1];
-    Q.rad = wbuf<double>(c, w[0], 4 * (size_t)N, st);
-    Q.lam = wbuf<double>(c, w[1], 4 * (size_t)N, st);
-    Q.raster = wbuf<double>(c, w[2], 2 * (size_t)N, st);
-    Q.depth = wbuf<uint32_t>(c, w[3], N, st);
-    Q.queries = wbuf<uint32_t>(c, w[4], N, st);
-    Q.p_valid = wbuf<uint32_t>(c, w[5], N, st);
-    Q.counts = wbuf<uint32_t>(c, w[6], (size_t)CNT_N * (1 + MAX_MERGE), st);  // + the merged passes' queues
-    for (int h = 0; h < 2; ++h) {
-        Q.qs[h].cap = (size_t)N;
-        Q.qs[h].d = wbuf<double>(c, w[7 + 3 * h], QD_N * (size_t)N, st);
-        Q.qs[h].r = wbuf<uint64_t>(c, w[8 + 3 * h], 2 * (size_t)N, st);
-        Q.qs[h].i = wbuf<int32_t>(c, w[9 + 3 * h], QI_N * (size_t)N, st);
+// Ray sorting of the split bounces' closest-hit rays (0: off)
+int ray_sort_mode(const Ctx& c) { return c.o.ray_sort >= 0 ? (int)c.o.ray_sort : (c.sc.stack_class >= 32 ? 1 : 0); }
+
+// A pass set: what one unit of passes in flight needs of its own.  Set 0 is the render's own Paths;
+// the pipelined schedules run their further units on sets 1..3.  Its buffers, as one list: the
+// per-pass outputs and counters (SET_OUT) and the ping-pong queues (SET_QUEUES), of `NV` virtual
+// slots (M merged passes' outputs and paths); for the split bounces the closest hits, the NEE
+// records and the ray sorting buffers (SET_HITS), of `cap` paths.
+enum { SET_OUT = 1, SET_QUEUES = 2, SET_HITS = 4, SET_ALL = 7 };
+struct SetRow {
+    int field, part;
+    size_t size, per_slot, per_cap, fixed;  // elements of `size` bytes: per_slot x NV + per_cap x cap + fixed
+};
+std::vector<SetRow> set_rows(int ns, bool sort) {
+    const size_t pairs = (size_t)NB * (size_t)ns;  // NEE pairs per path: bucket segments of `cap` paths each
+    std::vector<SetRow> r = {
+        {F_RAD, SET_OUT, 8, 4, 0, 0},       {F_LAM, SET_OUT, 8, 4, 0, 0},     {F_RASTER, SET_OUT, 8, 2, 0, 0},
+        {F_DEPTH, SET_OUT, 4, 1, 0, 0},     {F_QUERIES, SET_OUT, 4, 1, 0, 0}, {F_P_VALID, SET_OUT, 4, 1, 0, 0},
+        {F_COUNTS, SET_OUT, 4, 0, 0, (size_t)CNT_N * (1 + MAX_MERGE)},  // + the merged passes' queues
+        {F_QS0_D, SET_QUEUES, 8, QD_N, 0, 0},  {F_QS0_R, SET_QUEUES, 8, 2, 0, 0},  {F_QS0_I, SET_QUEUES, 4, QI_N, 0, 0},
+        {F_QS1_D, SET_QUEUES, 8, QD_N, 0, 0},  {F_QS1_R, SET_QUEUES, 8, 2, 0, 0},  {F_QS1_I, SET_QUEUES, 4, QI_N, 0, 0},
+        {F_HQ_T, SET_HITS, 8, 0, 1, 0},     {F_HQ_I, SET_HITS, 4, 0, 3, 0},
+        {F_SQ_D, SET_HITS, 8, 0, SD_N * pairs, 0},  {F_SQ_I, SET_HITS, 4, 0, SI_N * pairs, 0},
+        {F_SQ_HD, SET_HITS, 8, 0, (size_t)(ns > 1 ? SH_N : SH_N1) * NB, 0},
+        {F_SQ_HI, SET_HITS, 4, 0, (size_t)SHI_N * NB, 0}};
+    if (ns > 1) {
+        r.push_back({F_SQ_HR, SET_HITS, 8, 0, 2 * pairs, 0});
+        r.push_back({F_SQ_QL, SET_HITS, 4, 0, SHQ_CLASSES * pairs, 0});
+    }
+    if (sort) {  // keys and walk order, and the counting sort's workspace (scan.h RS_WORDS)
+        r.push_back({F_SORT_KEYS, SET_HITS, 4, 0, 1, 0});
+        r.push_back({F_SORT_ORDER, SET_HITS, 4, 0, 1, 0});
+        r.push_back({F_SORT_WS, SET_HITS, 4, 0, 0, RS_WORDS});
+    }
+    return r;
+}
+// Device bytes of one extra pass set of the split schedule (cap == NV): *fixed + *slot x NV.
+void split_set_bytes(const Ctx& c, size_t* slot, size_t* fixed) {
+    *slot = *fixed = 0;
+    for (const SetRow& r : set_rows(c.sc.n_shadow, ray_sort_mode(c) != 0)) {
+        *slot += r.size * (r.per_slot + r.per_cap);
+        *fixed += r.size * r.fixed;
     }
 }
-// Ray sorting buffers of pass set k (none when the option is off)
-int ray_sort_mode(const Ctx& c) { return c.o.ray_sort >= 0 ? (int)c.o.ray_sort : (c.sc.stack_class >= 32 ? 1 : 0); }
-// keys and walk order (cap each) and the counting sort's workspace (scan.h RS_WORDS), zeroed here
-// and by every sort's last block
-void alloc_sort(Ctx& c, HitQ& hq, int k, lumo_status& st) {
-    hq.perm = nullptr;
-    hq.keys = hq.order = hq.ws = nullptr;
-    if (!ray_sort_mode(c)) return;
-    const int w = W_SORT_SET0 + 3 * k;
-    hq.keys = wbuf<uint32_t>(c, w, hq.cap, st);
-    hq.order = wbuf<uint32_t>(c, w + 1, hq.cap, st);
-    hq.ws = wbuf<uint32_t>(c, w + 2, RS_WORDS, st);
-    if (!st && hipMemset(hq.ws, 0, sizeof(uint32_t) * RS_WORDS) != hipSuccess) st = LUMO_ERR_HIP;
-}
-
-// ... and, for the split schedule, the set's closest hits and NEE records (the sizes of set 0's)
-void alloc_split_set(Ctx& c, Paths& Q, const Paths& S, int k, int ns, lumo_status& st) {
-    const int w = W_SPLIT_SET1 + 8 * (k - 1);
-    Q.hq.t = wbuf<double>(c, w + 0, S.hq.cap, st);
-    Q.hq.i = wbuf<int32_t>(c, w + 1, 3 * S.hq.cap, st);
-    Q.sq.d = wbuf<double>(c, w + 2, SD_N * S.sq.cap, st);
-    Q.sq.i = wbuf<int32_t>(c, w + 3, SI_N * S.sq.cap, st);
-    Q.sq.hd = wbuf<double>(c, w + 4, (ns > 1 ? SH_N : SH_N1) * S.sq.hcap, st);
-    Q.sq.hi = wbuf<int32_t>(c, w + 5, SHI_N * S.sq.hcap, st);
-    Q.sq.hr = ns > 1 ? wbuf<uint64_t>(c, w + 6, 2 * S.sq.cap, st) : nullptr;
-    Q.sq.ql = ns > 1 ? wbuf<int32_t>(c, w + 7, SHQ_CLASSES * S.sq.cap, st) : nullptr;
-    alloc_sort(c, Q.hq, k, st);
-}
-// Device bytes of one extra pass set of the split schedule.
-size_t split_set_bytes(const Paths& S, int N, int ns) {
-    return (size_t)N * (4 + 4 + 2) * 8 + (size_t)N * 3 * 4 + 2 * (size_t)N * (QD_N * 8 + 16 + QI_N * 4) +
-           S.hq.cap * (8 + 12) + S.sq.cap * (SD_N * 8 + SI_N * 4) +
-           S.sq.hcap * ((ns > 1 ? SH_N : SH_N1) * 8 + SHI_N * 4) + (ns > 1 ? S.sq.cap * (4 * SHQ_CLASSES + 16) : 0) +
-           (S.hq.keys ? S.hq.cap * 8 + RS_WORDS * 4 : 0);  // the set's ray-sort keys, order and workspace
+// Allocates the `parts` of pass set k into Q (its other members are left as they are).
+void alloc_pass_set(Ctx& c, Paths& Q, int k, int parts, size_t NV, size_t cap, lumo_status& st) {
+    const int ns = c.sc.n_shadow;
+    void* p[F_SET_COUNT] = {};
+    for (const SetRow& r : set_rows(ns, ray_sort_mode(c) != 0))
+        if (r.part & parts)
+            p[r.field] = wbuf<char>(c, W_SET0 + k * F_SET_COUNT + r.field,
+                                    r.size * (r.per_slot * NV + r.per_cap * cap + r.fixed), st);
+    if (parts & SET_OUT) {
+        Q.rad = (double*)p[F_RAD];
+        Q.lam = (double*)p[F_LAM];
+        Q.raster = (double*)p[F_RASTER];
+        Q.depth = (uint32_t*)p[F_DEPTH];
+        Q.queries = (uint32_t*)p[F_QUERIES];
+        Q.p_valid = (uint32_t*)p[F_P_VALID];
+        Q.counts = (uint32_t*)p[F_COUNTS];
+    }
+    if (parts & SET_QUEUES)
+        for (int h = 0; h < 2; ++h)
+            Q.qs[h] = QState{(double*)p[F_QS0_D + 3 * h], (uint64_t*)p[F_QS0_R + 3 * h],
+                             (int32_t*)p[F_QS0_I + 3 * h], NV};
+    if (parts & SET_HITS) {
+        Q.hq = HitQ{(double*)p[F_HQ_T], (int32_t*)p[F_HQ_I], cap, nullptr, (uint32_t*)p[F_SORT_KEYS],
+                    (uint32_t*)p[F_SORT_ORDER], (uint32_t*)p[F_SORT_WS]};
+        Q.sq = ShadowQ{};
+        Q.sq.seg = (uint32_t)cap;
+        Q.sq.hcap = cap * NB;
+        Q.sq.cap = Q.sq.hcap * (size_t)ns;
+        Q.sq.d = (double*)p[F_SQ_D];
+        Q.sq.i = (int32_t*)p[F_SQ_I];
+        Q.sq.hd = (double*)p[F_SQ_HD];
+        Q.sq.hi = (int32_t*)p[F_SQ_HI];
+        Q.sq.hr = (uint64_t*)p[F_SQ_HR];
+        Q.sq.ql = (int32_t*)p[F_SQ_QL];
+        // the sort's workspace: zeroed here and by every sort's last block
+        if (Q.hq.ws && !st && hipMemset(Q.hq.ws, 0, sizeof(uint32_t) * RS_WORDS) != hipSuccess) st = LUMO_ERR_HIP;
+    }
 }
 
 // Error returns of the multi-stream schedulers: work already queued on the other streams may still
@@ -1026,6 +1047,125 @@ struct JoinOnError {
             if (c.streams[i]) (void)hipStreamSynchronize(c.streams[i]);
     }
 };
+
+// One render_impl call: the tasks' slots, the plan, the device state and what the schedulers report.
+struct Render {
+    const lumo_tile_task* tasks;
+    size_t n_tasks;
+    lumo_tile_result* out;
+    Dump* dump_host;  // a path dump (one task): the host arrays, dump_samples passes
+    uint64_t dump_samples;
+    std::vector<int32_t> first, task_of, pix_of;  // first slot of each task; task and pixel of each slot
+    int N = 0, dim_stride = 0;
+    uint64_t max_samples = 0, max_P = 0;
+    SchedPlan plan{};
+    Paths P[4] = {};  // the pass sets; P[0] is the render's own, the others share its per-slot state
+    Tasks T{};
+    Dump D{};
+    int dump_p = 0;
+    Bdpt B{};     // subpath vertices (the task groups add their redo lists and stores, render_bdpt_groups)
+    BItems BI{};  // connection work items
+    uint32_t* items_total = nullptr;
+    bool splat_lists = true;
+    uint32_t *tap_cnt = nullptr, *tap_off = nullptr;
+    double* dfilm = nullptr;
+    size_t film_n = 0;
+    std::vector<uint64_t> n_splats;
+    uint64_t bounces = 0;  // bounces that ran paths, from the count snapshots
+};
+
+// Count snapshots of a chain of bounces.  Bounces are enqueued ahead of the host's knowledge of the
+// queue counts: each bounce ends with an async copy of its counters into a pinned ring (slots
+// [base, base + len) of c.snap) and the host reads the snapshots back as their events complete.
+// Launch grids use the last known alive count `ub` as an upper bound (counts never grow within a
+// pass); the kernels read the exact counts from device memory.  A segment (a pass, a walk) is
+// `done` once a snapshot of it shows no path alive; the bounces enqueued past that point see empty
+// queues and exit at once, and their snapshots are consumed for the statistics by a later segment's
+// polls or re-recorded.  Snapshots are numbered over all segments; those issued before seg_first
+// update neither ub nor done.
+struct SnapCursor {
+    int base = 0, len = Ctx::SNAP_RING;
+    int issued = 0, consumed = 0, seg_first = 0;
+    uint32_t ub = 0;
+    bool done = false;
+    int outstanding() const { return issued - consumed; }
+    void begin_segment(uint32_t ub0) {
+        seg_first = issued;
+        ub = ub0;
+        done = false;
+    }
+    lumo_status record(Ctx& c, const uint32_t* counts, hipStream_t sm) {
+        const int slot = base + issued % len;
+        HIPCHK(hipMemcpyAsync(c.snap + CNT_N * slot, counts, sizeof(uint32_t) * CNT_N, hipMemcpyDeviceToHost, sm));
+        HIPCHK(hipEventRecord(c.snap_ev[slot], sm));
+        issued++;
+        return LUMO_OK;
+    }
+    // Takes the snapshots that have arrived, waiting for one while more than `keep` are outstanding
+    // (kNoWait: never).
+    static constexpr int kNoWait = Ctx::SNAP_RING;
+    lumo_status poll(Ctx& c, int keep, uint64_t& bounces) {
+        while (consumed < issued && !(done && consumed >= seg_first)) {
+            const int slot = base + consumed % len;
+            if (issued - consumed > keep) {
+                HIPCHK(hipEventSynchronize(c.snap_ev[slot]));
+            } else if (hipEventQuery(c.snap_ev[slot]) != hipSuccess) {
+                break;
+            }
+            const uint32_t* k = c.snap + CNT_N * slot;
+            bounces += k[CNT_CUR] > 0 ? 1 : 0;
+            if (consumed >= seg_first) {
+                ub = k[CNT_NEXT];
+                done = ub == 0;
+            }
+            consumed++;
+        }
+        return LUMO_OK;
+    }
+};
+
+// Film of a unit's `mu` passes from `pass0` (pass m's per-slot outputs `stride` virtual slots after
+// pass m - 1's in P) for tasks [t0, t1) whose tiles hold at most BLOCK pixels: one block per tile
+// (lumo's 16x16 tiles), the passes in pass order.
+void film_tiles(Ctx& c, const Render& R, hipStream_t sm, const Paths& P, uint64_t pass0, int mu, int stride, int t0,
+                int t1) {
+    StageTimer tm(c, c.o.timing, ST_FILM, sm);
+    k_finish_film<<<t1 - t0, BLOCK, 0, sm>>>(c.sc, P, R.T, c.cam, (uint32_t)pass0, R.D, R.dump_p, c.tone_map, c.tone_arg,
+                                             t0, mu, stride);
+}
+// Film of one pass (per-slot outputs V) for slots [s0, s1): tiles of any size.
+void film_large(Ctx& c, const Render& R, hipStream_t sm, const Paths& V, uint64_t pass, int s0, int s1) {
+    const int g = ceil_div(s1 - s0, BLOCK);
+    {
+        StageTimer tm(c, c.o.timing, ST_FINISH, sm);
+        k_finish<<<g, BLOCK, 0, sm>>>(c.sc, V, c.cam, s1, (uint32_t)pass, R.D, R.dump_p, c.tone_map, c.tone_arg, s0);
+    }
+    StageTimer tm(c, c.o.timing, ST_FILM, sm);
+    k_film<<<g, BLOCK, 0, sm>>>(V, R.T, c.cam, s1, s0);
+}
+
+// A merged unit's queue `head` of n_head paths after its head bounces, split by pass into segments
+// of `other` (the other ping-pong queue), each with counters of its own after the unit's.
+void split_merged_head(hipStream_t sm, const Paths& P, const QState& head, const QState& other, uint64_t n_head, int N,
+                       int mu) {
+    ZeroList z;
+    z.add(P.counts + CNT_N, sizeof(uint32_t) * CNT_N * (size_t)mu);
+    k_zero_list<<<1, BLOCK, 0, sm>>>(z);
+    k_split_passes<<<std::min(ceil_div(n_head, BLOCK), 4096), BLOCK, 0, sm>>>(head, other, P.counts, N, mu);
+}
+
+// One fused bounce (pt.h k_bounce_q) over at most `count` paths of queue `cur`; tail: the tail
+// kernel, which runs the paths of a queue shorter than `skip` to their end.
+void launch_fused_bounce(Ctx& c, hipStream_t sm, const Paths& P, const Tasks& T, const QState& cur, const QState& nxt,
+                         uint64_t count, uint32_t skip, bool tail) {
+    launch_trav(
+        c, count,
+        [&](auto K, const TravLaunch& l) {
+            launch_bounce_q<decltype(K)::value>(l, c.sc, P, T, cur, nxt, skip, tail, tail ? 0 : (int)c.o.dyn,
+                                                tail ? BLOCK : (int)c.o.bounce_threads);
+        },
+        sm);
+}
 
 // Pipelined passes (n_shadow == 1, fused bounces).  Russian roulette reads the pass's adaptive
 // delta only from depth RR_DEPTH on (path_trace.rs:60-69), and that delta needs the previous
@@ -1046,13 +1186,15 @@ struct JoinOnError {
 // concurrently; NA + 1 sets of queues, counters and per-slot outputs, a set reused only after
 // the unit NA + 1 back has issued its ring.  Every per-path operation and every film / ring sum
 // is the one the sequential loop performs, in the same order: bit-identical.
-lumo_status render_pipelined(Ctx& c, Paths& S, const Tasks& T, Dump& D, int dump_p, int N, int n_tasks, int dim_stride,
-                             uint64_t max_samples, uint64_t max_P, int M, lumo_status& st) {
-    const int NA = std::min(std::max((int)c.o.pipeline, 1), 3), NSETS = NA + 1;
+lumo_status render_pipelined(Ctx& c, Render& R) {
+    const Tasks& T = R.T;
+    const Dump& D = R.D;
+    const int N = R.N, n_tasks = (int)R.n_tasks, M = R.plan.M, heads = R.plan.head_bounces, bb = R.plan.tail_bounces;
+    const uint64_t max_samples = R.max_samples;
+    const bool tiles = R.max_P <= BLOCK;  // one film block per tile
+    const int NA = R.plan.head_streams, NSETS = NA + 1;
     JoinOnError join{c};
-    Paths P3[4] = {S, S, S, S};
-    for (int k = 1; k < NSETS; ++k) alloc_pass_set(c, P3[k], k, N * M, st);  // M passes' outputs and paths
-    if (st) return st;
+    Paths* P3 = R.P;
     hipStream_t As[3] = {c.streams[0], c.streams[2], c.streams[3]};
     hipStream_t B = c.streams[1];
     hipStream_t F = NA <= 2 ? c.streams[3] : B;  // the films (four streams: the device's hardware queues)
@@ -1071,16 +1213,6 @@ lumo_status render_pipelined(Ctx& c, Paths& S, const Tasks& T, Dump& D, int dump
         HIPCHK(hipEventRecord(c.film_ev[k], As[0]));
     }
     HIPCHK(hipStreamWaitEvent(B, c.pass_ev[0], 0));
-    // bounces on the head stream: through the RR bounce when a pass holds many paths; with fewer
-    // (a rank's share of a multi-GPU run) the RR bounce goes to the tail kernel too, so the head
-    // stream never waits for the previous pass's ring (362^2: 509 -> 434 ms).  Merged units
-    // (M > 1) always stop before it.
-    int heads = c.o.heads > 0 ? (int)c.o.heads : (N >= (1 << 21) ? RR_DEPTH + 1 : RR_DEPTH);
-    if (M > 1) heads = std::min(heads, RR_DEPTH);
-    c.sched.head_streams = NA;
-    c.sched.head_bounces = heads;
-    c.sched.merged_passes = M;
-    c.sched.tail_bounces = c.o.tail_bounces >= 0 ? (int)c.o.tail_bounces : (M == 1 ? 2 : 0);
     const int gN = ceil_div(N, BLOCK);
     const uint64_t units = (max_samples + (uint64_t)M - 1) / (uint64_t)M;
     for (uint64_t u = 0; u < units; ++u) {
@@ -1095,20 +1227,14 @@ lumo_status render_pipelined(Ctx& c, Paths& S, const Tasks& T, Dump& D, int dump
         if (NA > 1) HIPCHK(hipStreamWaitEvent(A, c.cam_ev[prev], 0));  // the previous unit's camera
         {
             StageTimer tm(c, c.o.timing, ST_CAMERA, A);
-            k_camera<true><<<gN, BLOCK, 0, A>>>(T, P, c.cam, N, dim_stride, (uint32_t)p0, 0, mu, N);
+            k_camera<true><<<gN, BLOCK, 0, A>>>(T, P, c.cam, N, R.dim_stride, (uint32_t)p0, 0, mu, N);
         }
         HIPCHK(hipEventRecord(c.cam_ev[set], A));
         for (int b = 0; b < heads; ++b) {
             if (b == RR_DEPTH) HIPCHK(hipStreamWaitEvent(A, c.pass_ev[prev], 0));  // this pass's delta (M == 1)
             k_bounce_begin<<<1, 64, 0, A>>>(P.counts, P.tcount + TC_HEADQ);
             StageTimer tm(c, c.o.timing, ST_CLOSEST, A);
-            launch_trav(
-                c, (uint64_t)N * mu,
-                [&](auto K, const TravLaunch& l) {
-                    launch_bounce_q<decltype(K)::value>(l, c.sc, P, T, P.qs[b & 1], P.qs[(b + 1) & 1], 0u, false,
-                                                        c.o.dyn, c.o.bounce_threads);
-                },
-                A);
+            launch_fused_bounce(c, A, P, T, P.qs[b & 1], P.qs[(b + 1) & 1], (uint64_t)N * mu, 0u, false);
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c.tail_ev[set], A));
@@ -1120,16 +1246,7 @@ lumo_status render_pipelined(Ctx& c, Paths& S, const Tasks& T, Dump& D, int dump
         // for the rest, the ring
         const QState& Qh = P.qs[heads & 1];
         const QState& Qs = P.qs[(heads + 1) & 1];
-        if (mu > 1) {
-            ZeroList z;
-            z.add(P.counts + CNT_N, sizeof(uint32_t) * CNT_N * (size_t)mu);
-            k_zero_list<<<1, BLOCK, 0, B>>>(z);
-            k_split_passes<<<std::min(ceil_div((uint64_t)N * mu, BLOCK), 4096), BLOCK, 0, B>>>(Qh, Qs, P.counts, N, mu);
-        }
-        // automatic: 2 for one-pass units (a full frame: its chain of tails and rings has room, and
-        // the bulk of the paths left after the head bounces runs at full throughput; C1 2 467 ->
-        // 2 380 ms), none for merged units (a rank's share: the tail stream is the critical chain)
-        const int bb = c.sched.tail_bounces;
+        if (mu > 1) split_merged_head(B, P, Qh, Qs, (uint64_t)N * mu, N, mu);
         for (int m = 0; m < mu; ++m) {
             const uint64_t pass = p0 + (uint64_t)m;
             Paths V = pass_view(P, m, N);
@@ -1140,60 +1257,34 @@ lumo_status render_pipelined(Ctx& c, Paths& S, const Tasks& T, Dump& D, int dump
             for (int b = 0; b < bb; ++b) {
                 k_bounce_begin<<<1, 64, 0, B>>>(Pm.counts, P.tcount + TC_HEADQ);
                 StageTimer tm(c, c.o.timing, ST_CLOSEST, B);
-                launch_trav(
-                    c, (uint64_t)N,
-                    [&](auto K, const TravLaunch& l) {
-                        launch_bounce_q<decltype(K)::value>(l, c.sc, Pm, T, (b & 1) ? q1 : q0, (b & 1) ? q0 : q1, 0u,
-                                                            false, c.o.dyn, c.o.bounce_threads);
-                    },
-                    B);
+                launch_fused_bounce(c, B, Pm, T, (b & 1) ? q1 : q0, (b & 1) ? q0 : q1, (uint64_t)N, 0u, false);
             }
             k_bounce_begin<<<1, 64, 0, B>>>(Pm.counts, P.tcount + TC_HEADQ);
             {
                 StageTimer tm(c, c.o.timing, ST_RESOLVE, B);
-                launch_trav(
-                    c, (uint64_t)N,
-                    [&](auto K, const TravLaunch& l) {
-                        launch_bounce_q<decltype(K)::value>(l, c.sc, Pm, T, (bb & 1) ? q1 : q0, (bb & 1) ? q0 : q1,
-                                                            0xffffffffu, true, 0, BLOCK);
-                    },
-                    B);
+                launch_fused_bounce(c, B, Pm, T, (bb & 1) ? q1 : q0, (bb & 1) ? q0 : q1, (uint64_t)N, 0xffffffffu,
+                                    true);
             }
             // the ring (which computes the samples' luminance itself): the next pass's Russian
             // roulette waits for it; the film is off that chain (film_first: the unit's film before
             // its last ring when they share stream B)
-            const bool film_here = max_P <= BLOCK && F == B && c.o.film_first && m == mu - 1;
-            if (film_here) {
-                StageTimer tm(c, c.o.timing, ST_FILM, B);
-                k_finish_film<<<n_tasks, BLOCK, 0, B>>>(c.sc, P, T, c.cam, (uint32_t)p0, D, dump_p, c.tone_map,
-                                                        c.tone_arg, 0, mu, N);
-            }
+            if (tiles && F == B && c.o.film_first && m == mu - 1) film_tiles(c, R, B, P, p0, mu, N, 0, n_tasks);
             {
                 StageTimer tm(c, c.o.timing, ST_RING, B);
                 k_ring<<<n_tasks, 64, 0, B>>>(c.sc, V, T, n_tasks, 1, m == mu - 1 ? P.counts : nullptr, 0);
             }
             HIPCHK(hipGetLastError());
-            if (max_P > BLOCK) {  // tiles larger than a block: per pass, on B
-                {
-                    StageTimer tm(c, c.o.timing, ST_FINISH, B);
-                    k_finish<<<gN, BLOCK, 0, B>>>(c.sc, V, c.cam, N, (uint32_t)pass, D, dump_p, c.tone_map, c.tone_arg,
-                                                  0);
-                }
-                StageTimer tm(c, c.o.timing, ST_FILM, B);
-                k_film<<<gN, BLOCK, 0, B>>>(V, T, c.cam, N, 0);
-            }
+            if (!tiles) film_large(c, R, B, V, pass, 0, N);  // tiles larger than a block: per pass, on B
         }
         HIPCHK(hipEventRecord(c.pass_ev[set], B));
         // the film of the unit's passes, one launch in pass order (after the previous unit's film on
         // the same stream), on a stream of its own when one is free
-        if (max_P <= BLOCK && !(F == B && c.o.film_first)) {
+        if (tiles && !(F == B && c.o.film_first)) {
             if (F != B) HIPCHK(hipStreamWaitEvent(F, c.pass_ev[set], 0));
-            StageTimer tm(c, c.o.timing, ST_FILM, F);
-            k_finish_film<<<n_tasks, BLOCK, 0, F>>>(c.sc, P, T, c.cam, (uint32_t)p0, D, dump_p, c.tone_map, c.tone_arg,
-                                                    0, mu, N);
+            film_tiles(c, R, F, P, p0, mu, N, 0, n_tasks);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipEventRecord(c.film_ev[set], max_P <= BLOCK ? F : B));
+        HIPCHK(hipEventRecord(c.film_ev[set], tiles ? F : B));
         if (c.o.timing) resolve_timers(c);
     }
     // the results are copied on stream 0: after every set's last unit and film
@@ -1211,7 +1302,7 @@ lumo_status render_pipelined(Ctx& c, Paths& S, const Tasks& T, Dump& D, int dump
 // on the live count (grids); the kernels read the exact count from S.counts.  allow_tail = false:
 // the bounce must not run paths through Russian roulette (a merged head, which reads no delta).
 constexpr uint32_t kSortMin = 1u << 15;  // ray sorting only for bounces with at least this many rays
-void issue_split_bounce(Ctx& c, Paths& S, const Tasks& T, const QState& cur, const QState& nxt, uint32_t ub,
+void issue_split_bounce(Ctx& c, const Paths& S, const Tasks& T, const QState& cur, const QState& nxt, uint32_t ub,
                         hipStream_t sm, bool fused_now, bool allow_tail = true) {
     const int ns = c.sc.n_shadow;
     // n_shadow == 1: the tail kernel takes the bounce when fewer than c.o.tail_below paths are alive
@@ -1223,15 +1314,11 @@ void issue_split_bounce(Ctx& c, Paths& S, const Tasks& T, const QState& cur, con
     const uint32_t skip = (allow_tail && ns == 1 && (uint64_t)ub < 4ull * c.o.tail_below) ? (uint32_t)c.o.tail_below : 0u;
     if (skip > 0) {
         StageTimer tm(c, c.o.timing, ST_RESOLVE, sm);
-        launch_trav(c, std::min(ub, skip), [&](auto K, const TravLaunch& l) {
-            launch_bounce_q<decltype(K)::value>(l, c.sc, S, T, cur, nxt, skip, true, 0, BLOCK);
-        }, sm);
+        launch_fused_bounce(c, sm, S, T, cur, nxt, std::min(ub, skip), skip, true);
     }
     if (fused_now) {  // one fused kernel per bounce (pt.h k_bounce_q)
         StageTimer tm(c, c.o.timing, ST_CLOSEST, sm);
-        launch_trav(c, ub, [&](auto K, const TravLaunch& l) {
-            launch_bounce_q<decltype(K)::value>(l, c.sc, S, T, cur, nxt, skip, false, c.o.dyn, c.o.bounce_threads);
-        }, sm);
+        launch_fused_bounce(c, sm, S, T, cur, nxt, ub, skip, false);
         return;
     }
     {   // the closest hits; with ray sorting, the rays' sort order first (timed as one closest-hit launch)
@@ -1309,27 +1396,17 @@ void issue_split_bounce(Ctx& c, Paths& S, const Tasks& T, const QState& cur, con
 // the oldest unit, which never waits for a unit the host has not finished issuing, and enqueues
 // every wait after the record it waits for.  Every per-path operation and every film / ring sum of
 // a task is the sequential loop's, in the same order: bit-identical.
-lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int n_tasks, int dim_stride,
-                                   uint64_t max_samples, uint64_t max_P, bool fused_now, int K, int G, int M,
-                                   const std::vector<int32_t>& first, uint64_t& bounces, lumo_status& st) {
+lumo_status render_split_pipelined(Ctx& c, Render& R) {
+    const Tasks& T = R.T;
+    const int N = R.N, K = R.plan.K, G = R.plan.G, M = R.plan.M;
+    const uint64_t max_samples = R.max_samples;
+    const bool fused_now = R.plan.fused;
+    const std::vector<int32_t>& first = R.first;
+    uint64_t& bounces = R.bounces;
     JoinOnError join{c};
     const int ns = c.sc.n_shadow;
-    G = std::max(1, std::min(G, std::min(K, n_tasks)));
-    // groups of consecutive tasks, about N / G slots each
-    std::vector<int> t_lo(G), t_hi(G);
-    for (int g = 0, t = 0; g < G; ++g) {
-        t_lo[g] = t;
-        const int64_t target = (int64_t)N * (g + 1) / G;
-        while (t < n_tasks && (g == G - 1 || first[t + 1] <= target || t == t_lo[g])) ++t;
-        t = std::max(std::min(t, n_tasks - (G - 1 - g)), t_lo[g] + 1);  // >= 1 task here and in every later group
-        t_hi[g] = t;
-    }
-    Paths P[4] = {S, S, S, S};
-    for (int k = 1; k < K; ++k) {
-        alloc_pass_set(c, P[k], k, N * M, st);  // M passes' outputs and paths
-        alloc_split_set(c, P[k], S, k, ns, st);
-    }
-    if (st) return st;
+    const std::vector<std::pair<int, int>> groups = task_groups(first.data(), (int)R.n_tasks, N, G);
+    Paths* P = R.P;
     {
         ZeroList z;
         for (int k = 1; k < K; ++k) z.add(P[k].counts, sizeof(uint32_t) * CNT_N);
@@ -1352,32 +1429,33 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
     struct PS {
         uint64_t unit, pass0;
         int g, set, mu, seg;
-        int issued, consumed, seg_first, seg_issued, head_issued;
-        uint32_t ub;
-        bool done, waited;
+        int seg_issued, head_issued;
+        bool waited;
+        SnapCursor s;
     };
     std::deque<PS> act;
     std::vector<uint64_t> finished(G, 0);  // passes of each group whose last ring has been issued
     const uint64_t per_group = (max_samples + (uint64_t)M - 1) / (uint64_t)M;
     const uint64_t units = per_group * (uint64_t)G;
     uint64_t next = 0;
-    auto group_slots = [&](int g) { return (uint32_t)(first[t_hi[g]] - first[t_lo[g]]); };
+    auto group_slots = [&](int g) { return (uint32_t)(first[groups[g].second] - first[groups[g].first]); };
     auto start = [&]() -> lumo_status {
         const int set = (int)(next % K), g = (int)(next % G);
         const uint64_t pass0 = (next / G) * (uint64_t)M;
         const int mu = (int)std::min<uint64_t>((uint64_t)M, max_samples - pass0);
         hipStream_t sm = c.streams[set];
-        const int s0 = first[t_lo[g]], s1 = first[t_hi[g]];
+        const int s0 = first[groups[g].first], s1 = first[groups[g].second];
         if (pass0 > 0) HIPCHK(hipStreamWaitEvent(sm, c.cam_ev[(next - G) % K], 0));  // sampler state per slot
         {
             StageTimer tm(c, c.o.timing, ST_CAMERA, sm);
-            k_camera<true><<<ceil_div(s1 - s0, BLOCK), BLOCK, 0, sm>>>(T, P[set], c.cam, s1, dim_stride, (uint32_t)pass0,
-                                                                        s0, mu, N);
+            k_camera<true><<<ceil_div(s1 - s0, BLOCK), BLOCK, 0, sm>>>(T, P[set], c.cam, s1, R.dim_stride,
+                                                                        (uint32_t)pass0, s0, mu, N);
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c.cam_ev[set], sm));
-        act.push_back(PS{next, pass0, g, set, mu, mu > 1 ? -1 : 0, 0, 0, 0, 0, 0, group_slots(g) * (uint32_t)mu, false,
-                         pass0 == 0});
+        PS ps{next, pass0, g, set, mu, mu > 1 ? -1 : 0, 0, 0, pass0 == 0, SnapCursor{set * SEG, SEG}};
+        ps.s.begin_segment(group_slots(g) * (uint32_t)mu);
+        act.push_back(ps);
         next++;
         return LUMO_OK;
     };
@@ -1390,7 +1468,7 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
     // the tail kernel (n_shadow == 1, launched once few paths are alive) runs paths to their end,
     // through Russian roulette, in whatever bounce it is launched: such a bounce needs the delta too
     auto tail_possible = [&](const PS& ps) {
-        return ns == 1 && c.o.tail_below > 0 && (uint64_t)ps.ub < 4ull * c.o.tail_below;
+        return ns == 1 && c.o.tail_below > 0 && (uint64_t)ps.s.ub < 4ull * c.o.tail_below;
     };
     // the queues and counters of the unit's current segment
     auto seg_paths = [&](const PS& ps) {
@@ -1418,51 +1496,25 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
         }
         Paths Q = seg_paths(ps);
         k_bounce_begin<<<1, 64, 0, sm>>>(Q.counts, Q.tcount + TC_HEADQ);
-        issue_split_bounce(c, Q, T, seg_queue(ps, ps.seg_issued & 1), seg_queue(ps, (ps.seg_issued + 1) & 1), ps.ub, sm,
-                           fused_now, ps.seg >= 0);
+        issue_split_bounce(c, Q, T, seg_queue(ps, ps.seg_issued & 1), seg_queue(ps, (ps.seg_issued + 1) & 1), ps.s.ub,
+                           sm, fused_now, ps.seg >= 0);
         HIPCHK(hipGetLastError());
-        const int slot = ps.set * SEG + ps.issued % SEG;
-        HIPCHK(hipMemcpyAsync(c.snap + CNT_N * slot, Q.counts, sizeof(uint32_t) * CNT_N, hipMemcpyDeviceToHost, sm));
-        HIPCHK(hipEventRecord(c.snap_ev[slot], sm));
-        ps.issued++;
+        const lumo_status e = ps.s.record(c, Q.counts, sm);
+        if (e) return e;
         ps.seg_issued++;
         if (ps.seg < 0) ps.head_issued++;
-        return LUMO_OK;
-    };
-    auto poll = [&](PS& ps, bool block) -> lumo_status {
-        while (ps.consumed < ps.issued && !(ps.done && ps.consumed >= ps.seg_first)) {
-            const int slot = ps.set * SEG + ps.consumed % SEG;
-            if (hipEventQuery(c.snap_ev[slot]) != hipSuccess) {
-                if (!block) break;
-                HIPCHK(hipEventSynchronize(c.snap_ev[slot]));
-                block = false;
-            }
-            const uint32_t* k = c.snap + CNT_N * slot;
-            bounces += k[CNT_CUR] > 0 ? 1 : 0;
-            if (ps.consumed >= ps.seg_first) {
-                ps.ub = k[CNT_NEXT];
-                ps.done = ps.ub == 0;
-            }
-            ps.consumed++;
-        }
         return LUMO_OK;
     };
     // the merged head is over (RR_DEPTH bounces, or no path left): its queue split by pass
     auto split = [&](PS& ps) -> lumo_status {
         hipStream_t sm = c.streams[ps.set];
         const Paths& Q = P[ps.set];
-        ZeroList z;
-        z.add(Q.counts + CNT_N, sizeof(uint32_t) * CNT_N * (size_t)ps.mu);
-        k_zero_list<<<1, BLOCK, 0, sm>>>(z);
-        const uint64_t n_head = (uint64_t)group_slots(ps.g) * (uint64_t)ps.mu;
-        k_split_passes<<<std::min(ceil_div(n_head, BLOCK), 4096), BLOCK, 0, sm>>>(
-            Q.qs[ps.head_issued & 1], Q.qs[(ps.head_issued + 1) & 1], Q.counts, N, ps.mu);
+        split_merged_head(sm, Q, Q.qs[ps.head_issued & 1], Q.qs[(ps.head_issued + 1) & 1],
+                          (uint64_t)group_slots(ps.g) * (uint64_t)ps.mu, N, ps.mu);
         HIPCHK(hipGetLastError());
         ps.seg = 0;
-        ps.seg_first = ps.issued;
         ps.seg_issued = 0;
-        ps.ub = group_slots(ps.g);
-        ps.done = false;
+        ps.s.begin_segment(group_slots(ps.g));
         return LUMO_OK;
     };
     // the ring of the segment's pass (task.rs:28-69, from the pass's final radiance); after the
@@ -1470,7 +1522,7 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
     auto finish = [&](PS& ps) -> lumo_status {
         hipStream_t sm = c.streams[ps.set];
         const Paths& Q = P[ps.set];
-        const int t0 = t_lo[ps.g], t1 = t_hi[ps.g], s0 = first[t0], s1 = first[t1];
+        const int t0 = groups[ps.g].first, t1 = groups[ps.g].second, s0 = first[t0], s1 = first[t1];
         const lumo_status w = wait_prev(ps);
         if (w) return w;
         const int m = ps.seg;
@@ -1482,30 +1534,16 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
         HIPCHK(hipGetLastError());
         if (!last) {  // the unit's next pass: its bounces follow this ring on the stream
             ps.seg = m + 1;
-            ps.seg_first = ps.issued;
             ps.seg_issued = 0;
-            ps.ub = group_slots(ps.g);
-            ps.done = false;
+            ps.s.begin_segment(group_slots(ps.g));
             return LUMO_OK;
         }
         HIPCHK(hipEventRecord(c.pass_ev[ps.set], sm));
         if (ps.pass0 > 0) HIPCHK(hipStreamWaitEvent(sm, c.film_ev[(ps.unit - G) % K], 0));
-        if (max_P <= BLOCK) {
-            StageTimer tm(c, c.o.timing, ST_FILM, sm);
-            k_finish_film<<<t1 - t0, BLOCK, 0, sm>>>(c.sc, Q, T, c.cam, (uint32_t)ps.pass0, Dump{}, 0, c.tone_map,
-                                                     c.tone_arg, t0, ps.mu, N);
-        } else {
-            for (int k = 0; k < ps.mu; ++k) {
-                const Paths V = pass_view(Q, k, N);
-                {
-                    StageTimer tm(c, c.o.timing, ST_FINISH, sm);
-                    k_finish<<<ceil_div(s1 - s0, BLOCK), BLOCK, 0, sm>>>(c.sc, V, c.cam, s1, (uint32_t)(ps.pass0 + k),
-                                                                         Dump{}, 0, c.tone_map, c.tone_arg, s0);
-                }
-                StageTimer tm(c, c.o.timing, ST_FILM, sm);
-                k_film<<<ceil_div(s1 - s0, BLOCK), BLOCK, 0, sm>>>(V, T, c.cam, s1, s0);
-            }
-        }
+        if (R.max_P <= BLOCK)
+            film_tiles(c, R, sm, Q, ps.pass0, ps.mu, N, t0, t1);
+        else
+            for (int k = 0; k < ps.mu; ++k) film_large(c, R, sm, pass_view(Q, k, N), ps.pass0 + (uint64_t)k, s0, s1);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c.film_ev[ps.set], sm));
         finished[ps.g] = ps.pass0 + (uint64_t)ps.mu;
@@ -1529,18 +1567,18 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
         }
         for (size_t i = 0; i < act.size(); ++i) {
             PS& ps = act[i];
-            if ((e = poll(ps, false))) return e;
+            if ((e = ps.s.poll(c, SnapCursor::kNoWait, bounces))) return e;
             if (ps.seg < 0) {  // merged head: RR_DEPTH bounces, then the split
-                if (ps.done || ps.seg_issued == RR_DEPTH) {
+                if (ps.s.done || ps.seg_issued == RR_DEPTH) {
                     if ((e = split(ps))) return e;
                     progress = true;
-                } else if (ps.issued - ps.consumed < ahead) {
+                } else if (ps.s.outstanding() < ahead) {
                     if ((e = issue(ps))) return e;
                     progress = true;
                 }
                 continue;
             }
-            if (ps.done) {
+            if (ps.s.done) {
                 if (ready(ps)) {  // the group's previous unit has issued its last ring
                     if ((e = finish(ps))) return e;
                     progress = true;
@@ -1553,14 +1591,14 @@ lumo_status render_split_pipelined(Ctx& c, Paths& S, const Tasks& T, int N, int 
             }
             // a bounce that reads the delta waits until the group's previous unit has issued its ring
             const bool may = !needs_delta(ps) || ready(ps);
-            if (may && ps.issued - ps.consumed < ahead) {
+            if (may && ps.s.outstanding() < ahead) {
                 if ((e = issue(ps))) return e;
                 progress = true;
             }
         }
         if (!progress) {
-            PS& f = act.front();  // the oldest unit waits for nothing the host has not issued
-            if ((e = poll(f, true))) return e;
+            PS& f = act.front();  // the oldest unit waits for nothing the host has not issued: its next snapshot
+            if ((e = f.s.poll(c, f.s.outstanding() - 1, bounces))) return e;
         }
     }
     // the results are copied on stream 0: after every set's last unit
@@ -1602,9 +1640,8 @@ struct BdGroup {
     uint32_t* totals;  // device: (a), (b) item totals of the pass
     uint64_t pass = 0;
     int phase = BD_LIGHT;
-    int issued = 0, consumed = 0, seg_first = 0, walk = 0;  // snapshots; bounces of the current walk
-    uint32_t ub = 0;
-    bool done = false;
+    SnapCursor s;  // the walks' count snapshots
+    int walk = 0;  // bounces of the current walk
     bool sort_ws_zeroed = false;  // the walk sort's workspace (zeroed once, then by every sort)
 };
 
@@ -1627,55 +1664,57 @@ VStore vstore_part(const VStore& v, int s0, int n) {
     return VStore{v.d + o * VD_N, v.i + o * VI_N, v.V, n, v.m + 2 * o, v.mf + o};
 }
 
-lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, int dump_p, const Bdpt& B,
-                               const BItems& BI, int N, int n_tasks, int dim_stride, uint64_t max_samples,
-                               uint64_t max_P, int G, const std::vector<int32_t>& first, uint32_t* items_total,
-                               bool splat_lists, double* dfilm, uint32_t* tap_cnt, uint32_t* tap_off,
-                               lumo_tile_result* out, std::vector<uint64_t>& n_splats, uint64_t& bounces,
-                               lumo_status& st) {
+// The view of slots s0 .. of the per-slot state: every per-slot pointer offset to slot s0 (a range of
+// consecutive slots is contiguous in every buffer).
+Paths slot_view(const Paths& S, int s0, int dim_stride) {
+    Paths P = S;
+    const size_t o = (size_t)s0;
+    auto at = [o](auto*& p, size_t per_slot) { p += per_slot * o; };
+    at(P.ro, 3), at(P.rd, 3), at(P.gath, 4), at(P.rad, 4), at(P.lam, 4), at(P.raster, 2), at(P.rng, 2);
+    at(P.depth, 1), at(P.flags, 1), at(P.queries, 1), at(P.task, 1), at(P.pix, 1), at(P.pseed, 1);
+    at(P.mj_rng, 2), at(P.mj_state, 1), at(P.perm, 2 * (size_t)dim_stride);
+    at(P.hit_t, 1), at(P.hit_kind, 1), at(P.hit_obj, 1), at(P.hit_tri, 1);
+    at(P.p_rgb, 3), at(P.p_valid, 1), at(P.film, 4), at(P.q0, 1), at(P.q1, 1);
+    return P;
+}
+BItems slot_view(const BItems& BI, int s0) {
+    BItems I = BI;
+    const size_t o = (size_t)s0;
+    auto at = [o](auto*& p, size_t per_slot) { p += per_slot * o; };
+    at(I.nl, 1), at(I.nc, 1), at(I.n_a, 1), at(I.off_a, 1), at(I.n_b, 1), at(I.off_b, 1), at(I.pdf, 1), at(I.wdepth, 1);
+    at(I.cam_o, 3), at(I.cam_d, 3), at(I.rng0, 2), at(I.lam0, 4);
+    return I;
+}
+
+lumo_status render_bdpt_groups(Ctx& c, Render& R) {
+    const Paths& S = R.P[0];
+    const Tasks& T = R.T;
+    const Dump& D = R.D;
+    const Bdpt& B = R.B;
+    const int N = R.N, G = R.plan.G;
+    const uint64_t max_samples = R.max_samples;
+    const std::vector<int32_t>& first = R.first;
+    lumo_tile_result* out = R.out;
+    std::vector<uint64_t>& n_splats = R.n_splats;
+    uint64_t& bounces = R.bounces;
+    double* dfilm = R.dfilm;
+    lumo_status st = LUMO_OK;
     JoinOnError join{c};
-    G = std::max(1, std::min(std::min(G, 4), n_tasks));
     std::vector<BdGroup> gr(G);
     const int V = B.lp.V, VR = BDPT_MAX_DEPTH + 1;
-    for (int g = 0, t = 0; g < G; ++g) {  // groups of consecutive tasks, about N / G slots each
+    const int SEG = Ctx::SNAP_RING / 4;  // snapshot slots per group
+    const std::vector<std::pair<int, int>> groups = task_groups(first.data(), (int)R.n_tasks, N, G);
+    for (int g = 0; g < G; ++g) {
         BdGroup& q = gr[g];
-        q.t0 = t;
-        const int64_t target = (int64_t)N * (g + 1) / G;
-        while (t < n_tasks && (g == G - 1 || first[t + 1] <= target || t == q.t0)) ++t;
-        t = std::max(std::min(t, n_tasks - (G - 1 - g)), q.t0 + 1);
-        q.t1 = t;
+        q.t0 = groups[g].first;
+        q.t1 = groups[g].second;
         q.s0 = first[q.t0];
         q.n = first[q.t1] - q.s0;
         q.sm = c.streams[g];
+        q.s = SnapCursor{g * SEG, SEG};
         const size_t o = (size_t)q.s0;
-        Paths& P = q.S;
-        P = S;
-        P.ro = S.ro + 3 * o;
-        P.rd = S.rd + 3 * o;
-        P.gath = S.gath + 4 * o;
-        P.rad = S.rad + 4 * o;
-        P.lam = S.lam + 4 * o;
-        P.raster = S.raster + 2 * o;
-        P.rng = S.rng + 2 * o;
-        P.depth = S.depth + o;
-        P.flags = S.flags + o;
-        P.queries = S.queries + o;
-        P.task = S.task + o;
-        P.pix = S.pix + o;
-        P.pseed = S.pseed + o;
-        P.mj_rng = S.mj_rng + 2 * o;
-        P.mj_state = S.mj_state + o;
-        P.perm = S.perm + 2 * (size_t)dim_stride * o;
-        P.hit_t = S.hit_t + o;
-        P.hit_kind = S.hit_kind + o;
-        P.hit_obj = S.hit_obj + o;
-        P.hit_tri = S.hit_tri + o;
-        P.p_rgb = S.p_rgb + 3 * o;
-        P.p_valid = S.p_valid + o;
-        P.film = S.film + 4 * o;
-        P.q0 = S.q0 + o;
-        P.q1 = S.q1 + o;
-        P.counts = S.counts + (size_t)g * CNT_N;  // zeroed at setup, then by the group's rings
+        q.S = slot_view(S, q.s0, R.dim_stride);
+        q.S.counts = S.counts + (size_t)g * CNT_N;  // zeroed at setup, then by the group's rings
         Bdpt& X = q.B;
         X = B;
         X.lp = vstore_part(B.lp, q.s0, q.n);
@@ -1698,27 +1737,13 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
         RR.sp = SplatStore{gbuf<double>(c, g, BG_RSP, (size_t)10 * VR * NR, st), gbuf<int32_t>(c, g, BG_RSPN, NR, st), VR, NR};
         RR.draws = gbuf<double>(c, g, BG_RDRAWS, (size_t)5 * VR * NR, st);
         RR.ok = gbuf<int32_t>(c, g, BG_ROK, (size_t)VR * NR, st);
-        BItems& I = q.I;
-        I = BI;
-        I.nl = BI.nl + o;
-        I.nc = BI.nc + o;
-        I.n_a = BI.n_a + o;
-        I.off_a = BI.off_a + o;
-        I.n_b = BI.n_b + o;
-        I.off_b = BI.off_b + o;
-        I.pdf = BI.pdf + o;
-        I.wdepth = BI.wdepth + o;
-        I.cam_o = BI.cam_o + 3 * o;
-        I.cam_d = BI.cam_d + 3 * o;
-        I.rng0 = BI.rng0 + 2 * o;
-        I.lam0 = BI.lam0 + 4 * o;
-        q.totals = items_total + 8 * g;
+        q.I = slot_view(R.BI, q.s0);
+        q.totals = R.items_total + 8 * g;
     }
     if (st) return st;
     // every group stream waits for the render's setup on stream 0 (tables, seeds, zeroing, ring)
     HIPCHK(hipEventRecord(c.pass_ev[0], c.streams[0]));
     for (int g = 1; g < G; ++g) HIPCHK(hipStreamWaitEvent(c.streams[g], c.pass_ev[0], 0));
-    const int SEG = Ctx::SNAP_RING / 4;
     const int ahead = std::max(1, std::min((int)c.o.bounce_ahead, SEG - 1));
     const int fx = c.sc.full;
     // walks: sorted on request (LUMO_OPT_RAY_SORT 1 / 2), and only with concurrent groups
@@ -1726,16 +1751,14 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
     auto start_walk = [&](BdGroup& q, int phase) {
         q.phase = phase;
         q.walk = 0;
-        q.seg_first = q.issued;
-        q.ub = (uint32_t)q.n;
-        q.done = false;
+        q.s.begin_segment((uint32_t)q.n);
     };
     auto start_pass = [&](BdGroup& q) -> lumo_status {
         // a path dump (one task, one group): the delta this pass's Russian roulette reads
         if (D.delta) HIPCHK(hipMemcpyAsync(D.delta + q.pass, T.delta, sizeof(double), hipMemcpyDeviceToDevice, q.sm));
         {
             StageTimer tm(c, c.o.timing, ST_CAMERA, q.sm);
-            k_camera<false><<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(T, q.S, c.cam, q.n, dim_stride, (uint32_t)q.pass, 0,
+            k_camera<false><<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(T, q.S, c.cam, q.n, R.dim_stride, (uint32_t)q.pass, 0,
                                                                        1, 0);
         }
         k_zero_counts<<<1, 64, 0, q.sm>>>(q.S.counts, q.B.redo_count);  // drop k_camera's queue; no re-runs yet
@@ -1752,7 +1775,7 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
         const int mode = q.phase == BD_LIGHT ? TR_IMPORTANCE : TR_RADIANCE;
         int32_t* qa = (q.walk & 1) ? q.S.q1 : q.S.q0;
         int32_t* qb = (q.walk & 1) ? q.S.q0 : q.S.q1;
-        const uint32_t ub = q.ub;
+        const uint32_t ub = q.s.ub;
         k_bounce_begin<<<1, 64, 0, q.sm>>>(q.S.counts, q.S.tcount + TC_HEADQ);
         const uint32_t skip = (uint64_t)ub < 4ull * c.o.bdpt_tail ? (uint32_t)c.o.bdpt_tail : 0u;
         if (walk_sort && skip == 0 && ub >= kSortMin) {  // the walk's rays sorted (lane order only)
@@ -1793,25 +1816,9 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
             });
         }
         HIPCHK(hipGetLastError());
-        const int slot = gi * SEG + q.issued % SEG;
-        HIPCHK(hipMemcpyAsync(c.snap + CNT_N * slot, q.S.counts, sizeof(uint32_t) * CNT_N, hipMemcpyDeviceToHost, q.sm));
-        HIPCHK(hipEventRecord(c.snap_ev[slot], q.sm));
-        q.issued++;
+        const lumo_status e = q.s.record(c, q.S.counts, q.sm);
+        if (e) return e;
         q.walk++;
-        return LUMO_OK;
-    };
-    auto poll = [&](BdGroup& q, int gi) -> lumo_status {
-        while (q.consumed < q.issued && !(q.done && q.consumed >= q.seg_first)) {
-            const int slot = gi * SEG + q.consumed % SEG;
-            if (hipEventQuery(c.snap_ev[slot]) != hipSuccess) break;
-            const uint32_t* k = c.snap + CNT_N * slot;
-            bounces += k[CNT_CUR] > 0 ? 1 : 0;
-            if (q.consumed >= q.seg_first) {
-                q.ub = k[CNT_NEXT];
-                q.done = q.ub == 0;
-            }
-            q.consumed++;
-        }
         return LUMO_OK;
     };
     // both walks done: re-runs, the item lists' scans and totals (read back through pinned memory)
@@ -1892,19 +1899,11 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
         }
         HIPCHK(hipGetLastError());
         const int s1 = q.s0 + q.n;
-        if (max_P <= BLOCK) {  // film and ring from the render's whole per-slot view, this group's tasks
-            StageTimer tm(c, c.o.timing, ST_FILM, q.sm);
-            k_finish_film<<<q.t1 - q.t0, BLOCK, 0, q.sm>>>(c.sc, S, T, c.cam, (uint32_t)q.pass, D, dump_p, c.tone_map,
-                                                            c.tone_arg, q.t0, 1, 0);
-        } else {
-            {
-                StageTimer tm(c, c.o.timing, ST_FINISH, q.sm);
-                k_finish<<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(c.sc, S, c.cam, s1, (uint32_t)q.pass, D, dump_p,
-                                                                  c.tone_map, c.tone_arg, q.s0);
-            }
-            StageTimer tm(c, c.o.timing, ST_FILM, q.sm);
-            k_film<<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(S, T, c.cam, s1, q.s0);
-        }
+        // film and ring from the render's whole per-slot view, this group's tasks
+        if (R.max_P <= BLOCK)
+            film_tiles(c, R, q.sm, S, q.pass, 1, 0, q.t0, q.t1);
+        else
+            film_large(c, R, q.sm, S, q.pass, q.s0, s1);
         {
             StageTimer tm(c, c.o.timing, ST_RING, q.sm);
             k_ring<<<q.t1 - q.t0, 64, 0, q.sm>>>(c.sc, S, T, q.t1, 1, q.S.counts, q.t0);
@@ -1914,9 +1913,9 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
             k_bdpt_taps<2><<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(c.sc, q.S, q.B, q.R, c.cam, q.n, c.tone_map,
                                                                       c.tone_arg, nullptr, nullptr, nullptr, dfilm);
             HIPCHK(hipGetLastError());
-        } else if (splat_lists) {  // this pass's taps in lumo's order, appended per task (blocking)
-            uint32_t* cnt = tap_cnt + q.s0;
-            uint32_t* off = tap_off + q.s0;
+        } else if (R.splat_lists) {  // this pass's taps in lumo's order, appended per task (blocking)
+            uint32_t* cnt = R.tap_cnt + q.s0;
+            uint32_t* off = R.tap_off + q.s0;
             k_bdpt_taps<0><<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(c.sc, q.S, q.B, q.R, c.cam, q.n, c.tone_map,
                                                                       c.tone_arg, cnt, nullptr, nullptr, nullptr);
             uint32_t* sums = gbuf<uint32_t>(c, gi, BG_SCAN, (size_t)scan_blocks(q.n), st);
@@ -1969,8 +1968,8 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
                 if (hipEventQuery(c.bd_ev[g]) == hipSuccess && (e = items(q, g))) return e;
                 continue;
             }
-            if ((e = poll(q, g))) return e;
-            if (q.done) {  // the walk has ended
+            if ((e = q.s.poll(c, SnapCursor::kNoWait, bounces))) return e;
+            if (q.s.done) {  // the walk has ended
                 if (q.phase == BD_LIGHT) {
                     k_zero_counts<<<1, 64, 0, q.sm>>>(q.S.counts, nullptr);
                     k_bdpt_cam_init<<<ceil_div(q.n, BLOCK), BLOCK, 0, q.sm>>>(q.S, q.B, q.I, c.cam, q.n);
@@ -1979,7 +1978,7 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
                 } else if ((e = after_walks(q, g))) {
                     return e;
                 }
-            } else if (q.issued - q.consumed < ahead) {
+            } else if (q.s.outstanding() < ahead) {
                 if ((e = issue_walk(q, g))) return e;
             }
         }
@@ -1994,81 +1993,125 @@ lumo_status render_bdpt_groups(Ctx& c, Paths& S, const Tasks& T, const Dump& D, 
     return LUMO_OK;
 }
 
-lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lumo_tile_result* out, Dump* dump_host,
-                        uint64_t dump_samples) {
-    if (!c.has_scene) return LUMO_ERR_NO_SCENE;
-    if (!c.has_camera) return LUMO_ERR_NO_CAMERA;
-    if (n_tasks == 0) return LUMO_OK;
-    // slots
-    std::vector<int32_t> first(n_tasks + 1), task_of, pix_of;
-    uint64_t max_total = 1, max_samples = 0, max_P = 0;
-    for (size_t i = 0; i < n_tasks; ++i) {
-        const lumo_tile_task& t = tasks[i];
+// The sequential loop: path tracing pass after pass on stream 0, without a pipeline.  It is the
+// baseline the pipelines are compared against and the route of a path dump of the split bounces.
+lumo_status render_sequential(Ctx& c, Render& R) {
+    const Paths& S = R.P[0];
+    const Tasks& T = R.T;
+    const int N = R.N, n_tasks = (int)R.n_tasks;
+    hipStream_t sm = c.streams[0];
+    // the host blocks only on the snapshot of the bounce `ahead` launches back (SnapCursor)
+    const int ahead = (int)c.o.bounce_ahead;
+    for (uint64_t pass = 0; pass < R.max_samples; ++pass) {
+        if (R.dump_host) HIPCHK(hipMemcpyAsync(R.D.delta + pass, T.delta, sizeof(double), hipMemcpyDeviceToDevice, sm));
+        // S.counts: zeroed at setup, then by the ring at the end of every pass
+        {
+            StageTimer tm(c, c.o.timing, ST_CAMERA);
+            k_camera<true><<<ceil_div(N, BLOCK), BLOCK, 0, sm>>>(T, S, c.cam, N, R.dim_stride, (uint32_t)pass, 0, 1, 0);
+        }
+        HIPCHK(hipGetLastError());
+        // Bounce loop over the alive queue (filled by the camera kernel just launched); the parity
+        // of the bounce selects the ping-pong queues.
+        SnapCursor s;  // the whole ring; the previous pass's slots and events are simply re-recorded
+        s.begin_segment((uint32_t)N);
+        for (;;) {
+            lumo_status e = s.poll(c, ahead - 1, R.bounces);
+            if (e) return e;
+            if (s.done) break;
+            k_bounce_begin<<<1, 64, 0, sm>>>(S.counts, S.tcount + TC_HEADQ);
+            issue_split_bounce(c, S, T, S.qs[s.issued & 1], S.qs[(s.issued + 1) & 1], s.ub, sm, R.plan.fused);
+            HIPCHK(hipGetLastError());
+            if ((e = s.record(c, S.counts, sm))) return e;
+        }
+        // The bounces issued past the first empty snapshot see empty queues; nothing waits for
+        // them: the stream orders them before the film kernels launched next (waiting here
+        // left the GPU idle for a host round trip per pass).
+        if (c.o.timing) resolve_timers(c);
+        if (R.max_P <= BLOCK)
+            film_tiles(c, R, sm, S, pass, 1, 0, 0, n_tasks);
+        else
+            film_large(c, R, sm, S, pass, 0, N);
+        {
+            StageTimer tm(c, c.o.timing, ST_RING);
+            k_ring<<<n_tasks, 64, 0, sm>>>(c.sc, S, T, n_tasks, 1, S.counts, 0);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return LUMO_OK;
+}
+
+// render_impl step 1: the tasks validated, one slot per pixel of every task.
+lumo_status build_slots(Render& R) {
+    R.first.resize(R.n_tasks + 1);
+    uint64_t max_total = 1;
+    for (size_t i = 0; i < R.n_tasks; ++i) {
+        const lumo_tile_task& t = R.tasks[i];
         if (!(t.px_max[0] > t.px_min[0] && t.px_max[1] > t.px_min[1]) || t.samples == 0 ||
             t.samples > SAMPLES_INCREMENT || t.total_samples == 0 ||
             t.px_max[0] > (uint64_t)1 << 31 || t.px_max[1] > (uint64_t)1 << 31)
             return LUMO_ERR_INVALID;
         const uint64_t P = (t.px_max[0] - t.px_min[0]) * (t.px_max[1] - t.px_min[1]);
-        max_P = std::max(max_P, P);
-        first[i] = (int32_t)task_of.size();
+        R.max_P = std::max(R.max_P, P);
+        R.first[i] = (int32_t)R.task_of.size();
         for (uint64_t j = 0; j < P; ++j) {
-            task_of.push_back((int32_t)i);
-            pix_of.push_back((int32_t)j);
+            R.task_of.push_back((int32_t)i);
+            R.pix_of.push_back((int32_t)j);
         }
-        if (task_of.size() > (1u << 30)) return LUMO_ERR_INVALID;
+        if (R.task_of.size() > (1u << 30)) return LUMO_ERR_INVALID;
         max_total = std::max(max_total, t.total_samples);
-        max_samples = std::max(max_samples, t.samples);
+        R.max_samples = std::max(R.max_samples, t.samples);
     }
-    first[n_tasks] = (int32_t)task_of.size();
-    const int N = (int)task_of.size();
-    const int ns = c.sc.n_shadow;
-    const int dim_stride = (int)std::ceil(std::sqrt((double)max_total));
-    if (dim_stride > 65535) return LUMO_ERR_INVALID;
+    R.first[R.n_tasks] = (int32_t)R.task_of.size();
+    R.N = (int)R.task_of.size();
+    R.dim_stride = (int)std::ceil(std::sqrt((double)max_total));
+    return R.dim_stride > 65535 ? LUMO_ERR_INVALID : LUMO_OK;
+}
 
-    lumo_status st = LUMO_OK;
-    const bool bdpt = c.integrator == LUMO_INTEGRATOR_BDPT;
-    // schedule: fused bounces (n_shadow == 1, the scene and the fused kernel's parked NEE records
-    // fit the LDS of a block) in the pipelined pass loop, which merges M passes per unit when a
-    // pass holds few paths (kMergeTarget); else the split schedule (below)
-    const bool fused_fits = (size_t)(c.sc.hot_bytes + 15u) / 16u * 16u +
-                                (size_t)PARK_DOUBLES * sizeof(double) * (size_t)c.o.bounce_threads <= c.lds_block;
-    const bool fused_now =
-        ns == 1 && (c.o.fused < 0 ? (c.o.lds && c.sc.hot_bytes > 0 && fused_fits) : c.o.fused != 0);
-    const bool pipe = !bdpt && fused_now && c.o.pipeline;
-    // the split schedule's pipeline (render_split_pipelined), when the free HBM allows (below)
-    const uint64_t split_units = max_samples * (uint64_t)std::max(1, std::min((int)c.o.split_groups, (int)n_tasks));
-    const bool split_try = !bdpt && !pipe && !dump_host && c.o.pipeline && c.o.split_pipe > 1 && split_units > 1;
-    int M = 1;
-    if (pipe || split_try) {  // merged passes: units of about kMergeTarget paths
-        M = (int)std::min<uint64_t>(MAX_MERGE, (kMergeTarget + N - 1) / (uint64_t)N);
-        // the split schedule merges passes only on request: at C3's 1/8 share merged units made the
-        // frame slower (M = 2 / 4 / 8: 723 -> 761 / 807 / 812 ms; the unit's large head launches
-        // hold the CUs while the latency-bound per-pass bounces of the group's chain wait; round 5)
-        if (split_try) M = 1;
-        if (c.o.merge > 0) M = (int)c.o.merge;
-        M = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)M, max_samples));
-        if ((uint64_t)N * (uint64_t)M > ((uint64_t)1 << 30)) M = 1;
+// Step 2: the schedule (sched_plan.h), from the options, the scene, the render's size and, where the
+// split schedule's pipeline is a candidate, the free device memory.
+SchedPlan plan_render(const Ctx& c, const Render& R) {
+    SchedIn in{};
+    in.fused = c.o.fused, in.lds = c.o.lds, in.pipeline = c.o.pipeline, in.heads = c.o.heads, in.merge = c.o.merge;
+    in.tail_bounces = c.o.tail_bounces, in.split_pipe = c.o.split_pipe, in.split_groups = c.o.split_groups;
+    in.bdpt_groups = c.o.bdpt_groups;
+    in.bdpt = c.integrator == LUMO_INTEGRATOR_BDPT;
+    in.dump = R.dump_host != nullptr;
+    in.n_shadow = c.sc.n_shadow, in.max_merge = MAX_MERGE, in.rr_depth = RR_DEPTH;
+    in.staged = c.sc.hot_bytes > 0;
+    in.fused_fits = (size_t)(c.sc.hot_bytes + 15u) / 16u * 16u +
+                        (size_t)PARK_DOUBLES * sizeof(double) * (size_t)c.o.bounce_threads <= c.lds_block;
+    in.N = R.N, in.n_tasks = (int)R.n_tasks, in.max_samples = R.max_samples;
+    if (plan_reads_hbm(in)) {
+        size_t total_b = 0;
+        split_set_bytes(c, &in.set_bytes_slot, &in.set_bytes_fixed);
+        in.held = c.split_sets_bytes;
+        in.hbm_known = hipMemGetInfo(&in.free_hbm, &total_b) == hipSuccess;
     }
-    const size_t NV = (size_t)N * (size_t)M;  // virtual slots: M passes' per-slot outputs
-    c.sched = lumo_schedule_info{};
-    c.sched.schedule = pipe ? LUMO_SCHED_FUSED_PIPELINE : LUMO_SCHED_SEQUENTIAL;
-    c.sched.fused = fused_now ? 1 : 0;
-    c.sched.merged_passes = 1;
-    c.sched.units_in_flight = 1;
-    c.sched.task_groups = 1;
-    Paths S{};
+    return plan_schedule(in);
+}
+
+// Step 3: the work buffers of the planned schedule: its pass sets, the per-slot state, the task
+// table, the dump and, for BDPT, the subpath and item stores.
+lumo_status alloc_render(Ctx& c, Render& R) {
+    const SchedPlan& plan = R.plan;
+    const int N = R.N;
+    const size_t n_tasks = R.n_tasks;
+    const bool bdpt = c.integrator == LUMO_INTEGRATOR_BDPT;
+    lumo_status st = LUMO_OK;
+    // M merged passes' outputs and paths per set; a merged unit of the split schedule runs its head
+    // bounces on the M passes' paths at once, the fused kernel needs no more hits and records than
+    // one pass's (MI355X has the HBM for the worst case)
+    const size_t NV = (size_t)N * (size_t)plan.M;
+    const size_t cap = plan.schedule == LUMO_SCHED_FUSED_PIPELINE ? (size_t)N : NV;
+    Paths& S = R.P[0];
+    alloc_pass_set(c, S, 0, bdpt ? SET_OUT : SET_ALL, NV, cap, st);
     // per slot: camera sampler, raster, final values; BDPT also its walk state
-    S.rad = wbuf<double>(c, W_RAD, 4 * NV, st);
-    S.lam = wbuf<double>(c, W_LAM, 4 * NV, st);
-    S.raster = wbuf<double>(c, W_RASTER, 2 * NV, st);
-    S.depth = wbuf<uint32_t>(c, W_DEPTH, NV, st);
-    S.queries = wbuf<uint32_t>(c, W_QUERIES, NV, st);
     S.task = wbuf<int32_t>(c, W_TASK, N, st);
     S.pix = wbuf<int32_t>(c, W_PIX, N, st);
     S.pseed = wbuf<uint64_t>(c, W_PSEED, N, st);
     S.mj_rng = wbuf<uint64_t>(c, W_MJRNG, 2 * (size_t)N, st);
     S.mj_state = wbuf<uint64_t>(c, W_MJSTATE, N, st);
-    S.perm = wbuf<uint16_t>(c, W_PERM, 2 * (size_t)dim_stride * N, st);
+    S.perm = wbuf<uint16_t>(c, W_PERM, 2 * (size_t)R.dim_stride * N, st);
     if (bdpt) {
         S.ro = wbuf<double>(c, W_RO, 3 * (size_t)N, st);
         S.rd = wbuf<double>(c, W_RD, 3 * (size_t)N, st);
@@ -2081,38 +2124,26 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         S.hit_tri = wbuf<int32_t>(c, W_HIT_TRI, N, st);
         S.q0 = wbuf<int32_t>(c, W_Q0, N, st);
         S.q1 = wbuf<int32_t>(c, W_Q1, N, st);
-    } else {
-        // path tracer: queue-order state (ping-pong), hits, NEE records (state.h); a merged unit of the
-        // split schedule runs its head bounces on the M passes' paths at once
-        const size_t cap = split_try ? NV : (size_t)N;
-        for (int k = 0; k < 2; ++k) {
-            S.qs[k].cap = NV;
-            S.qs[k].d = wbuf<double>(c, k ? W_QS1_D : W_QS0_D, QD_N * NV, st);
-            S.qs[k].r = wbuf<uint64_t>(c, k ? W_QS1_R : W_QS0_R, 2 * NV, st);
-            S.qs[k].i = wbuf<int32_t>(c, k ? W_QS1_I : W_QS0_I, QI_N * NV, st);
-        }
-        S.hq.cap = cap;
-        S.hq.t = wbuf<double>(c, W_HQ_T, cap, st);
-        S.hq.i = wbuf<int32_t>(c, W_HQ_I, 3 * cap, st);
-        alloc_sort(c, S.hq, 0, st);
-        // bucket segments of `cap` paths each (MI355X has the HBM for the worst case)
-        S.sq.seg = (uint32_t)cap;
-        S.sq.hcap = cap * NB;
-        S.sq.cap = S.sq.hcap * (size_t)ns;
-        S.sq.d = wbuf<double>(c, W_SQ_D, SD_N * S.sq.cap, st);
-        S.sq.i = wbuf<int32_t>(c, W_SQ_I, SI_N * S.sq.cap, st);
-        S.sq.hd = wbuf<double>(c, W_SQ_HD, (ns > 1 ? SH_N : SH_N1) * S.sq.hcap, st);
-        S.sq.hi = wbuf<int32_t>(c, W_SQ_HI, SHI_N * S.sq.hcap, st);
-        S.sq.hr = ns > 1 ? wbuf<uint64_t>(c, W_SQ_HR, 2 * S.sq.cap, st) : nullptr;
-        S.sq.ql = ns > 1 ? wbuf<int32_t>(c, W_SQ_QL, SHQ_CLASSES * S.sq.cap, st) : nullptr;
     }
     S.p_rgb = wbuf<double>(c, W_P_RGB, 3 * (size_t)N, st);
-    S.p_valid = wbuf<uint32_t>(c, W_P_VALID, NV, st);
     S.film = wbuf<double>(c, W_FILM, 4 * (size_t)N, st);
-    S.counts = wbuf<uint32_t>(c, W_COUNTS, (size_t)CNT_N * (1 + MAX_MERGE), st);  // + the merged passes' queues
     S.tcount = wbuf<unsigned long long>(c, W_TCOUNT, TC_ALL + TC_STATS, st);
     S.checks = wbuf<unsigned long long>(c, W_CHECKS, 3, st);
-    Tasks T{};
+    // the pipelines' further sets: the fused pipeline's share set 0's hits and NEE records
+    if (plan.schedule == LUMO_SCHED_FUSED_PIPELINE || plan.schedule == LUMO_SCHED_SPLIT_PIPELINE) {
+        const bool split = plan.schedule == LUMO_SCHED_SPLIT_PIPELINE;
+        const int sets = split ? plan.K : plan.head_streams + 1;
+        for (int k = 1; k < sets; ++k) {
+            R.P[k] = S;
+            alloc_pass_set(c, R.P[k], k, split ? SET_ALL : SET_OUT | SET_QUEUES, NV, cap, st);
+        }
+        if (split && !st) {
+            size_t slot = 0, fixed = 0;
+            split_set_bytes(c, &slot, &fixed);
+            c.split_sets_bytes = std::max(c.split_sets_bytes, (size_t)(plan.K - 1) * (fixed + slot * NV));
+        }
+    }
+    Tasks& T = R.T;
     T.t = wbuf<lumo_tile_task>(c, W_TASKS, n_tasks, st);
     T.first = wbuf<int32_t>(c, W_FIRST, n_tasks + 1, st);
     T.ring_cost = wbuf<uint64_t>(c, W_RING_COST, SAMPLES_INCREMENT * n_tasks, st);
@@ -2122,26 +2153,18 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
     T.sampler = c.sampler;
     T.num_rays = wbuf<unsigned long long>(c, W_NUM_RAYS, n_tasks, st);
     T.queries = wbuf<unsigned long long>(c, W_TQUERIES, n_tasks, st);
-    Dump D{};
-    int dump_p = 0;
-    if (dump_host) {
-        dump_p = N;  // single task
-        const size_t m = (size_t)dump_samples * N;
-        D.rad = wbuf<double>(c, W_DUMP_RAD, 4 * m, st);
-        D.lam = wbuf<double>(c, W_DUMP_LAM, 4 * m, st);
-        D.raster = wbuf<double>(c, W_DUMP_RASTER, 2 * m, st);
-        D.depth = wbuf<unsigned long long>(c, W_DUMP_DEPTH, m, st);
-        D.delta = wbuf<double>(c, W_DUMP_DELTA, dump_samples, st);
+    if (R.dump_host) {
+        R.dump_p = N;  // single task
+        const size_t m = (size_t)R.dump_samples * N;
+        R.D.rad = wbuf<double>(c, W_DUMP_RAD, 4 * m, st);
+        R.D.lam = wbuf<double>(c, W_DUMP_LAM, 4 * m, st);
+        R.D.raster = wbuf<double>(c, W_DUMP_RASTER, 2 * m, st);
+        R.D.depth = wbuf<unsigned long long>(c, W_DUMP_DEPTH, m, st);
+        R.D.delta = wbuf<double>(c, W_DUMP_DELTA, R.dump_samples, st);
     }
-    Bdpt B{};     // subpath vertices (the task groups add their redo lists and stores, render_bdpt_groups)
-    BItems BI{};  // connection work items
-    uint32_t* items_total = nullptr;
-    bool splat_lists = true;
-    uint32_t* tap_cnt = nullptr;
-    uint32_t* tap_off = nullptr;
-    double* dfilm = nullptr;
-    size_t film_n = 0;
     if (bdpt) {
+        Bdpt& B = R.B;
+        BItems& BI = R.BI;
         const int V = c.max_vertices;
         B.lp = VStore{wbuf<double>(c, W_BD_LD, (size_t)VD_N * V * N, st), wbuf<int32_t>(c, W_BD_LI, (size_t)VI_N * V * N, st), V, N,
                       wbuf<double>(c, W_BD_LM, (size_t)2 * V * N, st), wbuf<int32_t>(c, W_BD_LMF, (size_t)V * N, st)};
@@ -2165,27 +2188,34 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         BI.cam_d = wbuf<double>(c, W_BD_CAMD, 3 * (size_t)N, st);
         BI.rng0 = wbuf<uint64_t>(c, W_BD_RNG0, 2 * (size_t)N, st);
         BI.lam0 = wbuf<double>(c, W_BD_LAM0, 4 * (size_t)N, st);
-        items_total = wbuf<uint32_t>(c, W_BD_ITOTAL, 32, st);  // (a), (b) and the item lists' counts per task group
-        for (size_t i = 0; i < n_tasks && out; ++i) splat_lists = splat_lists && out[i].splats != nullptr;
-        if (!out) splat_lists = false;
-        if (splat_lists) {
-            tap_cnt = wbuf<uint32_t>(c, W_BD_CNT, N, st);
-            tap_off = wbuf<uint32_t>(c, W_BD_OFF, N, st);
+        R.items_total = wbuf<uint32_t>(c, W_BD_ITOTAL, 32, st);  // (a), (b) and the item lists' counts per task group
+        for (size_t i = 0; i < n_tasks && R.out; ++i) R.splat_lists = R.splat_lists && R.out[i].splats != nullptr;
+        if (!R.out) R.splat_lists = false;
+        if (R.splat_lists) {
+            R.tap_cnt = wbuf<uint32_t>(c, W_BD_CNT, N, st);
+            R.tap_off = wbuf<uint32_t>(c, W_BD_OFF, N, st);
         } else if (c.splat_film) {
-            film_n = (size_t)3 * (size_t)c.cam.width * (size_t)c.cam.height;
-            dfilm = wbuf<double>(c, W_BD_FILM, film_n, st);
-        } else if (out) {
+            R.film_n = (size_t)3 * (size_t)c.cam.width * (size_t)c.cam.height;
+            R.dfilm = wbuf<double>(c, W_BD_FILM, R.film_n, st);
+        } else if (R.out) {
             return LUMO_ERR_INVALID;  // BDPT splats need per-task lists or a splat film
         }
     }
-    if (st) return st;
+    return st;
+}
 
+// Step 4, on stream 0: the task and slot tables, the zeroing, the seeds and sampler permutations,
+// the initial ring.
+lumo_status setup_render(Ctx& c, Render& R) {
+    const Paths& S = R.P[0];
+    const Tasks& T = R.T;
+    const int N = R.N;
+    const size_t n_tasks = R.n_tasks;
     hipStream_t sm = c.streams[0];
-    std::vector<uint64_t> n_splats(n_tasks, 0);
-    HIPCHK(hipMemcpyAsync(T.t, tasks, sizeof(lumo_tile_task) * n_tasks, hipMemcpyHostToDevice, sm));
-    HIPCHK(hipMemcpyAsync(T.first, first.data(), sizeof(int32_t) * (n_tasks + 1), hipMemcpyHostToDevice, sm));
-    HIPCHK(hipMemcpyAsync(S.task, task_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, sm));
-    HIPCHK(hipMemcpyAsync(S.pix, pix_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, sm));
+    HIPCHK(hipMemcpyAsync(T.t, R.tasks, sizeof(lumo_tile_task) * n_tasks, hipMemcpyHostToDevice, sm));
+    HIPCHK(hipMemcpyAsync(T.first, R.first.data(), sizeof(int32_t) * (n_tasks + 1), hipMemcpyHostToDevice, sm));
+    HIPCHK(hipMemcpyAsync(S.task, R.task_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, sm));
+    HIPCHK(hipMemcpyAsync(S.pix, R.pix_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, sm));
     {
         ZeroList z;
         z.add(T.ring_cost, sizeof(uint64_t) * SAMPLES_INCREMENT * n_tasks);
@@ -2197,137 +2227,30 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         z.add(S.tcount, sizeof(unsigned long long) * (TC_ALL + TC_STATS));
         z.add(S.checks, sizeof(unsigned long long) * 3);
         z.add(S.counts, sizeof(uint32_t) * CNT_N * 4);  // + the BDPT task groups' counters
-        if (bdpt) {
-            z.add(B.overflow, sizeof(uint32_t) * 8);
-            if (dfilm) z.add(dfilm, sizeof(double) * film_n);
+        if (c.integrator == LUMO_INTEGRATOR_BDPT) {
+            z.add(R.B.overflow, sizeof(uint32_t) * 8);
+            if (R.dfilm) z.add(R.dfilm, sizeof(double) * R.film_n);
         }
         if (z.overflow) return LUMO_ERR_INVALID;
         k_zero_list<<<std::min(ceil_div((uint64_t)4 * N, BLOCK), 2048), BLOCK, 0, sm>>>(z);
     }
-
-    const int gT = ceil_div(n_tasks, BLOCK), gN = ceil_div(N, BLOCK);
-    k_init_seeds<<<gT, BLOCK, 0, sm>>>(T, S, (int)n_tasks);
-    k_init_mj<<<gN, BLOCK, 0, sm>>>(T, S, N, dim_stride);
+    k_init_seeds<<<ceil_div(n_tasks, BLOCK), BLOCK, 0, sm>>>(T, S, (int)n_tasks);
+    k_init_mj<<<ceil_div(N, BLOCK), BLOCK, 0, sm>>>(T, S, N, R.dim_stride);
     k_ring<<<(int)n_tasks, 64, 0, sm>>>(c.sc, S, T, (int)n_tasks, 0, nullptr, 0);
     HIPCHK(hipGetLastError());
+    return LUMO_OK;
+}
 
-    uint64_t bounces = 0, closest_q = 0, shadow_q = 0;
-    // Bounces are enqueued ahead of the host's knowledge of the queue counts: each bounce ends
-    // with an async copy of its counters into a pinned ring, and the host only blocks on the
-    // snapshot of the bounce `ahead` launches back.  Launch grids use the last known alive count
-    // as an upper bound (counts never grow within a pass); the kernels read the exact counts from
-    // device memory.  A pass ends once a snapshot shows no path alive; the bounces enqueued past
-    // that point see empty queues and exit at once.
-    const int ahead = (int)c.o.bounce_ahead;
-    if (pipe) {
-        const lumo_status ps = render_pipelined(c, S, T, D, dump_p, N, (int)n_tasks, dim_stride, max_samples, max_P, M, st);
-        if (ps) return ps;
-        if (st) return st;
-    }
-    // split schedule: units in flight, as many as c.o.split_pipe and the free HBM allow
-    int K = 1;
-    if (split_try) {
-        size_t free_b = 0, total_b = 0;
-        const size_t per_set = split_set_bytes(S, (int)NV, ns);
-        const size_t margin = (size_t)8 << 30;
-        const uint64_t units = (max_samples + (uint64_t)M - 1) / (uint64_t)M *
-                               (uint64_t)std::max(1, std::min((int)c.o.split_groups, (int)n_tasks));
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            K = std::min(std::min((int)c.o.split_pipe, 4), (int)std::min<uint64_t>(units, 4));
-            while (K > 1 && (size_t)(K - 1) * per_set + margin > free_b + c.split_sets_bytes) K--;
-        }
-    }
-    if (K > 1) {
-        c.sched.schedule = LUMO_SCHED_SPLIT_PIPELINE;
-        c.sched.units_in_flight = K;
-        c.sched.task_groups = std::max(1, std::min((int)c.o.split_groups, std::min(K, (int)n_tasks)));
-        c.sched.merged_passes = M;
-        const lumo_status ps = render_split_pipelined(c, S, T, N, (int)n_tasks, dim_stride, max_samples, max_P,
-                                                      fused_now, K, (int)c.o.split_groups, M, first, bounces, st);
-        if (ps) return ps;
-        if (st) return st;
-        c.split_sets_bytes = std::max(c.split_sets_bytes, (size_t)(K - 1) * split_set_bytes(S, (int)NV, ns));
-    }
-    // BDPT: every render runs the task groups' pass body (render_bdpt_groups): concurrent chains of
-    // passes for several tasks; one chain (G = 1, reported as the sequential schedule) for a single
-    // task, on request (LUMO_OPT_BDPT_GROUPS 1) and for a path dump
-    if (bdpt) {
-        const int G = dump_host ? 1 : std::min(std::min((int)c.o.bdpt_groups, 4), (int)n_tasks);
-        if (G > 1) {
-            c.sched.schedule = LUMO_SCHED_BDPT_GROUPS;
-            c.sched.task_groups = G;
-            c.sched.units_in_flight = G;
-        }
-        const lumo_status ps = render_bdpt_groups(c, S, T, D, dump_p, B, BI, N, (int)n_tasks, dim_stride, max_samples,
-                                                  max_P, G, first, items_total, splat_lists, dfilm, tap_cnt, tap_off,
-                                                  out, n_splats, bounces, st);
-        if (ps) return ps;
-        if (st) return st;
-    }
-    // the sequential loop: path tracing without a pipeline
-    for (uint64_t pass = 0; pass < ((bdpt || pipe || K > 1) ? 0 : max_samples); ++pass) {
-        if (dump_host) HIPCHK(hipMemcpyAsync(D.delta + pass, T.delta, sizeof(double), hipMemcpyDeviceToDevice, sm));
-        // S.counts: zeroed at setup, then by the ring at the end of every pass
-        {
-            StageTimer tm(c, c.o.timing, ST_CAMERA);
-            k_camera<true><<<gN, BLOCK, 0, sm>>>(T, S, c.cam, N, dim_stride, (uint32_t)pass, 0, 1, 0);
-        }
-        HIPCHK(hipGetLastError());
-        // Bounce loop over the alive queue (filled by the camera kernel just launched); the parity
-        // of the bounce selects the ping-pong queues.  Bounces are enqueued ahead of the host's
-        // knowledge of the counts; see above.
-        uint32_t ub = (uint32_t)N;  // upper bound on the alive count of the next bounce
-        int issued = 0, consumed = 0;
-        bool done = false;
-        for (;;) {
-            while (consumed < issued) {
-                hipEvent_t e = c.snap_ev[consumed % Ctx::SNAP_RING];
-                if (issued - consumed >= ahead) {
-                    HIPCHK(hipEventSynchronize(e));
-                } else if (hipEventQuery(e) != hipSuccess) {
-                    break;
-                }
-                const uint32_t* k = c.snap + CNT_N * (consumed % Ctx::SNAP_RING);
-                bounces += k[CNT_CUR] > 0 ? 1 : 0;
-                ub = k[CNT_NEXT];
-                done = done || ub == 0;
-                consumed++;
-            }
-            if (done) break;
-            k_bounce_begin<<<1, 64, 0, sm>>>(S.counts, S.tcount + TC_HEADQ);
-            issue_split_bounce(c, S, T, S.qs[issued & 1], S.qs[(issued + 1) & 1], ub, sm, fused_now);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(c.snap + CNT_N * (issued % Ctx::SNAP_RING), S.counts, sizeof(uint32_t) * CNT_N,
-                                  hipMemcpyDeviceToHost, sm));
-            HIPCHK(hipEventRecord(c.snap_ev[issued % Ctx::SNAP_RING], sm));
-            issued++;
-        }
-        // The bounces issued past the first empty snapshot see empty queues; nothing waits for
-        // them: the stream orders them before the film kernels launched next (waiting here
-        // left the GPU idle for a host round trip per pass), and their snapshot slots and
-        // events are simply re-recorded by the next pass.
-        if (c.o.timing) resolve_timers(c);
-        if (max_P <= BLOCK) {  // one block per tile (lumo's 16x16 tiles)
-            StageTimer tm(c, c.o.timing, ST_FILM);
-            k_finish_film<<<(int)n_tasks, BLOCK, 0, sm>>>(c.sc, S, T, c.cam, (uint32_t)pass, D, dump_p, c.tone_map,
-                                                          c.tone_arg, 0, 1, 0);
-        } else {
-            {
-                StageTimer tm(c, c.o.timing, ST_FINISH);
-                k_finish<<<gN, BLOCK, 0, sm>>>(c.sc, S, c.cam, N, (uint32_t)pass, D, dump_p, c.tone_map, c.tone_arg, 0);
-            }
-            {
-                StageTimer tm(c, c.o.timing, ST_FILM);
-                k_film<<<gN, BLOCK, 0, sm>>>(S, T, c.cam, N, 0);
-            }
-        }
-        {
-            StageTimer tm(c, c.o.timing, ST_RING);
-            k_ring<<<(int)n_tasks, 64, 0, sm>>>(c.sc, S, T, (int)n_tasks, 1, S.counts, 0);
-        }
-        HIPCHK(hipGetLastError());
-    }
-    // results
+// Step 6: the tiles, counters and dump read back on stream 0; the results and statistics filled.
+lumo_status read_back(Ctx& c, Render& R) {
+    const Paths& S = R.P[0];
+    const Tasks& T = R.T;
+    const int N = R.N;
+    const size_t n_tasks = R.n_tasks;
+    lumo_tile_result* out = R.out;
+    const std::vector<int32_t>& first = R.first;
+    const bool bdpt = c.integrator == LUMO_INTEGRATOR_BDPT;
+    hipStream_t sm = c.streams[0];
     // Per-task {sum w*rgb, sum w} tiles: straight into the caller's buffers when they are laid out
     // back to back in slot order (the Python wrapper allocates them so), else via a host copy.
     bool direct = out != nullptr && n_tasks > 0 && out[0].rgb_w != nullptr;
@@ -2343,34 +2266,35 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
     unsigned long long tc[TC_ALL], checks[3];
     HIPCHK(hipMemcpyAsync(tc, S.tcount, sizeof(tc), hipMemcpyDeviceToHost, sm));
     HIPCHK(hipMemcpyAsync(checks, S.checks, sizeof(checks), hipMemcpyDeviceToHost, sm));
-    if (dump_host) {
-        const size_t m = (size_t)dump_samples * N;
-        HIPCHK(hipMemcpyAsync(dump_host->rad, D.rad, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, sm));
-        HIPCHK(hipMemcpyAsync(dump_host->lam, D.lam, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, sm));
-        HIPCHK(hipMemcpyAsync(dump_host->raster, D.raster, sizeof(double) * 2 * m, hipMemcpyDeviceToHost, sm));
-        HIPCHK(hipMemcpyAsync(dump_host->depth, D.depth, sizeof(unsigned long long) * m, hipMemcpyDeviceToHost, sm));
-        HIPCHK(hipMemcpyAsync(dump_host->delta, D.delta, sizeof(double) * dump_samples, hipMemcpyDeviceToHost, sm));
+    if (R.dump_host) {
+        const Dump& D = R.D;
+        const size_t m = (size_t)R.dump_samples * N;
+        HIPCHK(hipMemcpyAsync(R.dump_host->rad, D.rad, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, sm));
+        HIPCHK(hipMemcpyAsync(R.dump_host->lam, D.lam, sizeof(double) * 4 * m, hipMemcpyDeviceToHost, sm));
+        HIPCHK(hipMemcpyAsync(R.dump_host->raster, D.raster, sizeof(double) * 2 * m, hipMemcpyDeviceToHost, sm));
+        HIPCHK(hipMemcpyAsync(R.dump_host->depth, D.depth, sizeof(unsigned long long) * m, hipMemcpyDeviceToHost, sm));
+        HIPCHK(hipMemcpyAsync(R.dump_host->delta, D.delta, sizeof(double) * R.dump_samples, hipMemcpyDeviceToHost, sm));
     }
     HIPCHK(hipStreamSynchronize(sm));
     if (c.o.timing) resolve_timers(c);
     bool splat_oom = false;
     if (bdpt) {
         uint32_t ovf[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (overflow, redo count) per task group
-        HIPCHK(hipMemcpy(ovf, B.overflow, sizeof(ovf), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ovf, R.B.overflow, sizeof(ovf), hipMemcpyDeviceToHost));
         if (ovf[0] | ovf[2] | ovf[4] | ovf[6]) return LUMO_ERR_UNSUPPORTED;  // more long subpaths in one pass than a redo list holds
-        if (dfilm) {
-            std::vector<double> f(film_n);
-            HIPCHK(hipMemcpy(f.data(), dfilm, sizeof(double) * film_n, hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < film_n; ++k) c.splat_film[k] += f[k];
+        if (R.dfilm) {
+            std::vector<double> f(R.film_n);
+            HIPCHK(hipMemcpy(f.data(), R.dfilm, sizeof(double) * R.film_n, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < R.film_n; ++k) c.splat_film[k] += f[k];
         }
         for (size_t i = 0; i < n_tasks && out; ++i) {
-            out[i].num_splats = n_splats[i];
-            splat_oom = splat_oom || (splat_lists && n_splats[i] > out[i].splat_cap);
+            out[i].num_splats = R.n_splats[i];
+            splat_oom = splat_oom || (R.splat_lists && R.n_splats[i] > out[i].splat_cap);
         }
     }
     for (size_t i = 0; i < n_tasks; ++i) {
         if (!out) break;
-        const lumo_tile_task& t = tasks[i];
+        const lumo_tile_task& t = R.tasks[i];
         const size_t P = (size_t)(first[i + 1] - first[i]);
         if (out[i].rgb_w && !direct)
             std::memcpy(out[i].rgb_w, film.data() + 4 * (size_t)first[i], sizeof(double) * 4 * P);
@@ -2378,17 +2302,14 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
         out[i].num_rays = rays[i];
         out[i].num_queries = queries[i];
     }
-    {
-        unsigned long long total_q = 0;
-        for (size_t i = 0; i < n_tasks; ++i) total_q += queries[i];
-        // per-slot query counters: PT 1 per closest + 1 per valid record; BDPT walk traces (the
-        // bounce snapshots) + connection / re-run queries
-        closest_q = tc[TC_HEADQ] + tc[TC_TAILQ];  // bounce heads + the tail kernel's further bounces
-        shadow_q = total_q >= closest_q ? total_q - closest_q : 0;
-    }
+    unsigned long long total_q = 0;
+    for (size_t i = 0; i < n_tasks; ++i) total_q += queries[i];
+    // per-slot query counters: PT 1 per closest + 1 per valid record; BDPT walk traces (the
+    // bounce snapshots) + connection / re-run queries
+    const uint64_t closest_q = tc[TC_HEADQ] + tc[TC_TAILQ];  // bounce heads + the tail kernel's further bounces
     c.stats.closest_queries += closest_q;
-    c.stats.shadow_queries += shadow_q;
-    c.stats.bounces += bounces;
+    c.stats.shadow_queries += total_q >= closest_q ? total_q - closest_q : 0;
+    c.stats.bounces += R.bounces;
     c.stats.samples_nan += checks[0];
     c.stats.samples_neg += checks[1];
     c.stats.samples_large += checks[2];
@@ -2409,6 +2330,33 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
     }
 #endif
     return splat_oom ? LUMO_ERR_OOM : LUMO_OK;
+}
+
+// A render: validate and build slots, plan, allocate, set up on stream 0, run the planned
+// scheduler, read back.
+lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lumo_tile_result* out, Dump* dump_host,
+                        uint64_t dump_samples) {
+    if (!c.has_scene) return LUMO_ERR_NO_SCENE;
+    if (!c.has_camera) return LUMO_ERR_NO_CAMERA;
+    if (n_tasks == 0) return LUMO_OK;
+    Render R{tasks, n_tasks, out, dump_host, dump_samples};
+    R.n_splats.assign(n_tasks, 0);
+    lumo_status st = build_slots(R);
+    if (st) return st;
+    const SchedPlan& p = R.plan = plan_render(c, R);
+    c.sched = lumo_schedule_info{p.schedule, p.head_streams, p.head_bounces, p.M,
+                                 p.K,        p.G,            p.fused ? 1 : 0, p.tail_bounces};
+    if ((st = alloc_render(c, R))) return st;
+    if ((st = setup_render(c, R))) return st;
+    switch (p.schedule) {
+        case LUMO_SCHED_FUSED_PIPELINE: st = render_pipelined(c, R); break;
+        case LUMO_SCHED_SPLIT_PIPELINE: st = render_split_pipelined(c, R); break;
+        case LUMO_SCHED_BDPT_GROUPS: st = render_bdpt_groups(c, R); break;
+        default:  // one chain of passes on stream 0: BDPT's pass body with one group, or the path tracer's loop
+            st = c.integrator == LUMO_INTEGRATOR_BDPT ? render_bdpt_groups(c, R) : render_sequential(c, R);
+    }
+    if (st) return st;
+    return read_back(c, R);
 }
 
 }  // namespace

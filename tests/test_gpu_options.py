@@ -531,6 +531,29 @@ def test_large_tiles_split_pipeline(merge):
     _assert_query_totals(before, after, cnt)
 
 
+def test_large_tiles_bdpt_groups():
+    """The two 32x48 tasks on Cornell through the BDPT task groups, one task per group, at 2 spp: each
+    group's film is k_finish + k_film per pass on the group's stream, over the group's slots of the
+    render's whole per-slot view.  Tiles, counts and per-task splat lists equal the oracle's."""
+    sc, cam, tasks = _cornell(), L.Camera.cornell_box((64, 48)), _large_tasks(2)
+    osp = []
+    obufs, ores, _ = _oracle(sc, cam, tasks, integrator=BDPT, splats_out=osp)
+    d = _device(bdpt_groups=2)
+    try:
+        d.upload(sc, cam)
+        sp = []
+        bufs, res, before, after = _render_counted(d, tasks, integrator=BDPT, splats_out=sp, max_vertices=6)
+        sch = d.last_schedule()
+    finally:
+        d.close()
+    assert (sch.schedule, sch.task_groups) == (3, 2)
+    # k_finish once per group and pass, as the camera (the wrapper renders again if a splat list was short)
+    cameras = stage_launches(before, after, "camera")
+    assert cameras >= 2 * 2 and stage_launches(before, after, "finish") == cameras
+    assert_tiles_equal(bufs, res, obufs, ores, camera_rays=True)
+    assert_splats_equal(sp, osp)
+
+
 # ---------------------------------------------------------------------------- 7. pixel filter footprints
 FILTERS = [(1.5, 0.2), (1.0, 0.5), (0.6, 0.375), (1.5, 3.0)]
 

@@ -6,19 +6,23 @@
 //      marble, Mandelbrot, bump map, textured light), both integrators;
 //   3. the decoders on hostile input: truncated and bit-flipped PNG / HDR files and mangled
 //      OBJ / MTL text must fail cleanly (or load) without any sanitizer report;
-//   4. the tile-task generator and instance transforms.
+//   4. the tile-task generator and instance transforms;
+//   5. the render schedulers' plan and task groups (csrc/common/sched_plan.h) against recorded plans.
 // Any ASan / UBSan finding aborts the process (halt_on_error), which the test treats as failure.
 #include <zlib.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/lumo_host.h"
+#include "../../lumo_amd/csrc/common/sched_plan.h"
 #include "../../oracle/oracle.h"
 
 namespace {
@@ -302,9 +306,207 @@ void brute() {
     lumo_builder_free(b);
 }
 
+// The schedule plan (sched_plan.h plan_schedule) against the plans the device code chose before the
+// plan was one function.  "test": the tuple a GPU test asserts through lumo_last_schedule; the other
+// fields of those rows, and the rows without a test, were evaluated by hand from the expressions of
+// lumo_amd/csrc/device/kernels.hip at commit 655ab47 (cited by line).
+void plans() {
+    using lumo::dev::SchedIn;
+    using lumo::dev::SchedPlan;
+    const size_t GiB = (size_t)1 << 30, plenty = 256 * GiB;
+    // the default options (ctx.h Opts), a staged n_shadow == 1 scene that fits (Cornell), no memory figures
+    SchedIn c1{};
+    c1.fused = -1, c1.lds = 1, c1.pipeline = 3, c1.heads = 0, c1.merge = 0, c1.tail_bounces = -1;
+    c1.split_pipe = 4, c1.split_groups = 2, c1.bdpt_groups = 2;
+    c1.n_shadow = 1, c1.staged = true, c1.fused_fits = true, c1.max_merge = 8, c1.rr_depth = 5;  // state.h
+    c1.N = 1536 * 1536, c1.n_tasks = 96 * 96, c1.max_samples = 8;
+    // C3: n_shadow == 11, too large to stage; 7 000 B per slot and set (a figure of the right size), plenty free
+    SchedIn c3 = c1;
+    c3.n_shadow = 11, c3.staged = false, c3.fused_fits = false;
+    c3.N = 1920 * 1080, c3.n_tasks = 8160, c3.max_samples = 2;
+    c3.set_bytes_slot = 7000, c3.set_bytes_fixed = 1 << 16, c3.free_hbm = plenty, c3.held = 0, c3.hbm_known = true;
+    const size_t c3_set = c3.set_bytes_fixed + c3.set_bytes_slot * (size_t)c3.N;
+    // the 64x48 mid-size scenes of tests/test_gpu_scale.py: 12 tasks, 9 spp
+    SchedIn mid = c3;
+    mid.N = 64 * 48, mid.n_tasks = 12, mid.max_samples = 9;
+    struct Case {
+        const char* name;
+        SchedIn in;
+        SchedPlan want;  // schedule, fused, M, K, G, head streams, head bounces, tail bounces
+    };
+    std::vector<Case> cases;
+    auto add = [&](const char* name, SchedIn in, SchedPlan want) { cases.push_back({name, in, want}); };
+    // test_gpu_parity.py test_headline_schedule_matches_oracle: (1, 3 streams, 6 heads, M 1, tail 2)
+    add("headline", c1, {1, true, 1, 1, 1, 3, 6, 2});
+    {   // ... its second render, pipeline 0: schedule 0 (2037, 2040: no pipeline, no split)
+        SchedIn in = c1;
+        in.pipeline = 0;
+        add("headline, pipeline 0", in, {0, true, 1, 1, 1, 0, 0, 0});
+    }
+    {   // test_share_schedule_matches_sequential_and_oracle: (1, 3, M 8); heads min(5, RR_DEPTH) (1078-1079),
+        // tail bounces 0 for merged units (1083)
+        SchedIn in = c1;
+        in.N = 131072, in.n_tasks = 512, in.max_samples = 24;
+        add("C1 share", in, {1, true, 8, 1, 1, 3, 5, 0});
+        in.max_samples = 3;  // M <= max_samples (2049)
+        add("C1 share, 3 spp", in, {1, true, 3, 1, 1, 3, 5, 0});
+        in.heads = 7, in.tail_bounces = 1, in.pipeline = 1;  // test_gpu_options.py: heads capped for merged units
+        add("C1 share, options", in, {1, true, 3, 1, 1, 1, 5, 1});
+        in.merge = 1, in.pipeline = 5;  // one-pass units keep the requested heads; at most 3 head streams (1051)
+        add("C1 share, merge 1", in, {1, true, 1, 1, 1, 3, 7, 1});
+    }
+    {   // N x M > 2^30: M falls to 1 (2050); N >= 2^21: 6 heads
+        SchedIn in = c1;
+        in.N = 1 << 28, in.merge = 8;
+        add("huge pass", in, {1, true, 1, 1, 1, 3, 6, 2});
+    }
+    {   // a dump of a fused scene runs the fused pipeline (2037 has no dump term; the smoke run's path dump):
+        // 32x32, 4 spp: M = min(8, 2048, 4) (2043-2049)
+        SchedIn in = c1;
+        in.dump = true, in.N = 1024, in.n_tasks = 1, in.max_samples = 4;
+        add("fused dump", in, {1, true, 4, 1, 1, 3, 5, 0});
+    }
+    {   // fused by option and by fit (2033-2036)
+        SchedIn in = c1;
+        in.fused_fits = false;
+        in.hbm_known = true, in.free_hbm = plenty, in.set_bytes_slot = 700;
+        add("does not fit", in, {2, false, 1, 4, 2, 0, 0, 0});
+        in.fused = 1;
+        add("fused forced", in, {1, true, 1, 1, 1, 3, 6, 2});
+        in.fused = 0, in.fused_fits = true;
+        add("fused off", in, {2, false, 1, 4, 2, 0, 0, 0});
+        in.fused = -1, in.lds = 0;
+        add("lds off", in, {2, false, 1, 4, 2, 0, 0, 0});
+    }
+    // test_gpu_scale.py test_c3_bench_schedule_full_frame: (2, K 4, G 2, fused 0); M 1 (2047)
+    add("C3 frame", c3, {2, false, 1, 4, 2, 0, 0, 0});
+    {   // a dump of the split bounces: sequential (2040)
+        SchedIn in = c3;
+        in.dump = true, in.N = 1024, in.n_tasks = 1, in.max_samples = 4;
+        add("split dump", in, {0, false, 1, 1, 1, 0, 0, 0});
+    }
+    {   // split_pipe 1: sequential, whatever merge asks (test_c3_share_merged_passes' second render; 2040)
+        SchedIn in = c3;
+        in.split_pipe = 1, in.merge = 8;
+        add("split_pipe 1", in, {0, false, 1, 1, 1, 0, 0, 0});
+    }
+    {   // free memory (2232-2237): K - 1 extra sets and the 8 GiB margin must fit in free + held
+        SchedIn in = c3;
+        in.free_hbm = 9 * GiB;
+        add("low memory", in, {0, false, 1, 1, 1, 0, 0, 0});
+        in.free_hbm = 8 * GiB + c3_set;
+        add("one extra set fits", in, {2, false, 1, 2, 2, 0, 0, 0});
+        in.free_hbm = 8 * GiB + 2 * c3_set - 1;
+        add("two extra sets do not", in, {2, false, 1, 2, 2, 0, 0, 0});
+        in.held = 1;
+        add("... with the byte held", in, {2, false, 1, 3, 2, 0, 0, 0});
+        in.free_hbm = 0, in.held = 8 * GiB + 3 * c3_set;
+        add("sets already held", in, {2, false, 1, 4, 2, 0, 0, 0});
+        in.hbm_known = false;  // the query failed (2235)
+        add("memory unknown", in, {0, false, 1, 1, 1, 0, 0, 0});
+    }
+    {   // test_c3_share_merged_passes: (2, K 4, G 2, M 8)
+        SchedIn in = c3;
+        in.N = 261120, in.n_tasks = 1020, in.max_samples = 16, in.merge = 8;
+        add("C3 share, merge 8", in, {2, false, 8, 4, 2, 0, 0, 0});
+    }
+    // test_split_pipeline_passes_in_flight (k, groups): (2, k, min(groups, k)); k = 1: schedule 0
+    for (int k = 1; k <= 4; ++k)
+        for (int groups : {1, 2, 3, 4}) {
+            SchedIn in = mid;
+            in.split_pipe = k, in.split_groups = groups, in.merge = 1;
+            add("units in flight", in, k == 1 ? SchedPlan{0, false, 1, 1, 1, 0, 0, 0}
+                                              : SchedPlan{2, false, 1, k, std::min(groups, k), 0, 0, 0});
+        }
+    {   // test_split_merged_passes (merge, k, groups): (2, k, min(groups, k), M merge); a forced merge with
+        // the split schedule
+        const int rows[5][3] = {{8, 4, 2}, {2, 4, 2}, {3, 3, 1}, {8, 4, 4}, {4, 2, 2}};
+        for (const auto& r : rows) {
+            SchedIn in = mid;
+            in.merge = r[0], in.split_pipe = r[1], in.split_groups = r[2];
+            add("split, merged", in, {2, false, r[0], r[1], std::min(r[2], r[1]), 0, 0, 0});
+        }
+        SchedIn in = mid;  // fewer units than sets: 9 passes in units of 8, one group: 2 units (2233-2236)
+        in.merge = 8, in.split_groups = 1;
+        add("split, two units", in, {2, false, 8, 2, 1, 0, 0, 0});
+        in.max_samples = 1, in.n_tasks = 1;  // one unit: nothing to pipeline (2039-2040)
+        add("split, one unit", in, {0, false, 1, 1, 1, 0, 0, 0});
+    }
+    {   // BDPT (2255-2259, 1637): test_gpu_bdpt.py (3, groups) for several tasks, (0, 1) for one group
+        SchedIn in = c1;
+        in.bdpt = true, in.N = 1024, in.n_tasks = 1, in.max_samples = 4;
+        add("BDPT, one task", in, {0, true, 1, 1, 1, 0, 0, 0});
+        in.N = 64 * 48, in.n_tasks = 12;
+        add("BDPT, 12 tasks", in, {3, true, 1, 2, 2, 0, 0, 0});
+        in.bdpt_groups = 9;
+        add("BDPT, 9 groups asked", in, {3, true, 1, 4, 4, 0, 0, 0});
+        in.n_tasks = 3;
+        add("BDPT, 3 tasks", in, {3, true, 1, 3, 3, 0, 0, 0});
+        in.bdpt_groups = 1;
+        add("BDPT, groups 1", in, {0, true, 1, 1, 1, 0, 0, 0});
+        in.bdpt_groups = 0;
+        add("BDPT, groups 0", in, {0, true, 1, 1, 1, 0, 0, 0});
+        in.bdpt_groups = 2, in.n_tasks = 1, in.dump = true;
+        add("BDPT dump", in, {0, true, 1, 1, 1, 0, 0, 0});
+        in = c3, in.bdpt = true;
+        add("BDPT, C3", in, {3, false, 1, 2, 2, 0, 0, 0});
+    }
+    for (const Case& k : cases) {
+        const SchedPlan p = lumo::dev::plan_schedule(k.in);
+        const SchedPlan& w = k.want;
+        if (p.schedule != w.schedule || p.fused != w.fused || p.M != w.M || p.K != w.K || p.G != w.G ||
+            p.head_streams != w.head_streams || p.head_bounces != w.head_bounces || p.tail_bounces != w.tail_bounces) {
+            std::fprintf(stderr, "plan \"%s\": got (%d, %d, M %d, K %d, G %d, %d, %d, %d)\n", k.name, p.schedule, (int)p.fused,
+                         p.M, p.K, p.G, p.head_streams, p.head_bounces, p.tail_bounces);
+            std::exit(2);
+        }
+    }
+}
+
+// task_groups (sched_plan.h) on 1, 2, 3 and 40 tasks of unequal size, every G <= min(4, tasks): the
+// ranges are consecutive, cover the tasks, hold a task each, and are the ones the loop of
+// kernels.hip:1319-1326 at commit 655ab47 yields (run on these sizes; the second 3-task case by hand).
+void groups() {
+    struct Case {
+        std::vector<int> sizes;
+        int G;
+        std::vector<std::pair<int, int>> want;
+    };
+    std::vector<int> forty;
+    for (int i = 0; i < 40; ++i) forty.push_back(1 + (i * 7) % 11);
+    const std::vector<Case> cases = {
+        {{5}, 1, {{0, 1}}},
+        {{3, 10}, 1, {{0, 2}}},
+        {{3, 10}, 2, {{0, 1}, {1, 2}}},
+        {{7, 1, 4}, 1, {{0, 3}}},
+        {{7, 1, 4}, 2, {{0, 1}, {1, 3}}},
+        {{7, 1, 4}, 3, {{0, 1}, {1, 2}, {2, 3}}},
+        {{1, 1, 10}, 3, {{0, 1}, {1, 2}, {2, 3}}},  // the first group would take two tasks: one is left for each later group
+        {forty, 1, {{0, 40}}},
+        {forty, 2, {{0, 20}, {20, 40}}},
+        {forty, 3, {{0, 14}, {14, 26}, {26, 40}}},
+        {forty, 4, {{0, 9}, {9, 20}, {20, 29}, {29, 40}}},
+    };
+    for (const Case& k : cases) {
+        const int n = (int)k.sizes.size();
+        std::vector<int32_t> first(1, 0);
+        for (int sz : k.sizes) first.push_back(first.back() + sz);
+        const std::vector<std::pair<int, int>> g = lumo::dev::task_groups(first.data(), n, first.back(), k.G);
+        CHECK((int)g.size() == k.G);
+        CHECK(g.front().first == 0 && g.back().second == n);
+        for (int i = 0; i < k.G; ++i) {
+            CHECK(g[(size_t)i].second > g[(size_t)i].first);
+            if (i) CHECK(g[(size_t)i].first == g[(size_t)i - 1].second);
+        }
+        CHECK(g == k.want);
+    }
+}
+
 }  // namespace
 
 int main() {
+    plans();
+    groups();
     cornell();
     brute();
     textured();

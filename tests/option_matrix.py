@@ -70,5 +70,12 @@ OPTION_MATRIX = {
     "bdpt_groups": Row(1, 4, None, 2, [(1, _B + "test_bdpt_task_groups"), (4, _B + "test_bdpt_task_groups")], None),
     "ray_sort": Row(-1, 2, None, -1, [(1, _S + "test_ray_sort_matches_oracle"), (2, _B + "test_bdpt_walk_ray_sort")],
                     None),
-    "accel": Row(0, 1, None, 0, [(1, "tests/test_gpu_wide.py::test_wide_cornell_fused_tiles")], None),
+    "accel": Row(0, 1, None, 0, [(1, "tests/test_gpu_wide.py::test_wide_cornell_fused_tiles")] +
+                 [(1, "tests/test_gpu_wide_forms.py::" + t) for t in (
+                     "test_wide_kernel_variants", "test_wide_split_kernels_staged", "test_wide_bounce_modes_small_dragon",
+                     "test_wide_fused_pipeline_staged", "test_wide_top_prefix_edges", "test_wide_whole_tree_in_top",
+                     "test_wide_top_cut_in_blas", "test_wide_split_pipeline", "test_wide_bdpt_walk_forms",
+                     "test_wide_bdpt_top_visibility", "test_wide_bdpt_task_groups",
+                     "test_wide_bdpt_long_subpaths_are_rerun", "test_wide_bdpt_walk_ray_sort",
+                     "test_wide_refusal_and_boundary")], None),
 }

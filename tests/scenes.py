@@ -234,6 +234,103 @@ def stadium():
     return s
 
 
+# ---- light kd trees at the wide accel's depth limit (wbvh.h LIGHT_KD_STACK; tests/test_wide.py,
+# tests/test_gpu_wide_forms.py)
+def light_kd_depth(desc):
+    """Deepest level of a light's kd tree, the root counted as level 1 (0: no light has a tree), over
+    the lights wbvh::build looks at: kd meshes and rectangles with a root."""
+    deepest = 0
+    for i in range(desc.num_lights):
+        o = desc.lights[i]
+        if o.type not in (0, 1) or o.kd_root < 0:  # LUMO_OBJ_KDMESH, LUMO_OBJ_RECTANGLE
+            continue
+        stack = [(o.kd_root, 1)]
+        while stack:
+            k, level = stack.pop()
+            if k < 0 or k >= desc.num_kd_nodes:
+                continue
+            deepest = max(deepest, level)
+            if not desc.kd_nodes[k].leaf:
+                stack += [(k + 1, level + 1), (desc.kd_nodes[k].right, level + 1)]
+    return deepest
+
+
+def knot_light_scene(n, m):
+    """A torus_knot_tube(n, m) mesh added as a light.  The builder turns a light mesh into one triangle
+    light per face (Scene::add_mesh), so no light of such a scene has a kd tree, whatever n and m."""
+    from lumo_amd.procedural import torus_knot_tube
+    v, f = torus_knot_tube(n, m)
+    s = L.Scene()
+    s.add_mesh(v, f, L.Material.light(L.Spectrum.from_rgb(1.0, 0.8, 0.6), scale=0.5), light=True)
+    return s
+
+
+class DeepLightScene:
+    """A floor, a small grey knot and one tilted rectangle light whose kd tree is `levels` deep.
+
+    The only lights with a kd tree are rectangles (two triangles, one or two levels), so the depth
+    comes from the scene description, not from the builder: the description of the built scene is
+    copied with the light's tree re-rooted under a chain of interior nodes.  Chain node j splits the
+    light's box at a plane inside it (x and z in turn); its left child is the next chain node (the
+    last one's: a copy of the original tree) and its right child another copy of the original tree.
+    Both triangles stay reachable on either side of every plane, as triangles that straddle a kd
+    split are, so it is a valid kd tree of the same rectangle and rays that cross the planes push
+    the far side.  upload() and the oracle take it as any scene (desc())."""
+
+    def __init__(self, levels):
+        import ctypes as C
+
+        from lumo_amd import _ffi
+        from lumo_amd.procedural import torus_knot_tube
+        s = L.Scene()
+        s.add_rectangle((-3, -1, -3), (3, -1, -3), (3, -1, 3), _grey())
+        v, f = torus_knot_tube(25, 4)
+        s.add_mesh(0.5 * (v - v.mean(0)) / np.abs(v - v.mean(0)).max() + (0.2, -0.4, 0.1), f, _grey())
+        s.add_rectangle((-0.5, 2.0, -0.5), (0.5, 2.3, -0.5), (0.5, 2.3, 0.5), L.Material.light(NS("WHITE")), light=True)
+        self._base = s.build()
+        d = self._base.desc()
+        assert d.num_lights == 1 and d.lights[0].type == 1 and d.lights[0].kd_root >= 0
+        own = light_kd_depth(d)
+        assert 1 <= own <= levels
+        nodes = [d.kd_nodes[i] for i in range(d.num_kd_nodes)]
+
+        def copy_tree(i):  # lumo's layout: the left child follows its parent
+            src = d.kd_nodes[i]
+            at = len(nodes)
+            nodes.append(_ffi.KdNode(src.point, src.axis, src.right, src.leaf, src.first, src.count, 0))
+            if not src.leaf:
+                assert copy_tree(i + 1) == at + 1
+                nodes[at].right = copy_tree(src.right)
+            return at
+
+        old_root = d.lights[0].kd_root
+        chain = levels - own
+        lo, hi = d.lights[0].bmin, d.lights[0].bmax
+        first = len(nodes)
+        for j in range(chain):
+            axis = (0, 2)[j % 2]
+            point = lo[axis] + (hi[axis] - lo[axis]) * (j + 1) / (chain + 1)
+            nodes.append(_ffi.KdNode(point, axis, -1, 0, 0, 0, 0))
+        root = copy_tree(old_root)  # follows the last chain node: its left child
+        assert chain == 0 or root == first + chain
+        for j in range(chain):
+            nodes[first + j].right = copy_tree(old_root)
+        self._nodes = (_ffi.KdNode * len(nodes))(*nodes)
+        self._lights = (_ffi.Object * 1)()
+        C.memmove(self._lights, d.lights, C.sizeof(_ffi.Object))
+        self._lights[0].kd_root = first if chain else root
+        self._desc = _ffi.SceneDesc()
+        C.memmove(C.byref(self._desc), C.byref(d), C.sizeof(_ffi.SceneDesc))
+        self._desc.kd_nodes, self._desc.num_kd_nodes = self._nodes, len(nodes)
+        self._desc.lights = self._lights
+
+    def build(self):
+        return self
+
+    def desc(self):
+        return self._desc
+
+
 EDGE_SCENES = {"concentric": (concentric_triangles, (0.3, 2.0, 1.0)), "degenerate": (degenerate_mesh, (0.0, 0.5, 4.0)),
                "flat": (flat_mesh, (0.2, 2.0, 0.5)),
                "zoo_translated": (translated_zoo, ZOO_SHIFT),

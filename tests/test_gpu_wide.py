@@ -150,8 +150,13 @@ def test_wide_dragon_split_tiles(dev):
     sc = scenes.dragon(torus_knot_tube(300, 12))
     cam = scenes.default_camera((48, 32))
     dev.upload(sc, cam)
+    info = dev.scene_info()
+    assert info.accel == 1 and info.lds_bytes == 0 and info.n_shadow == 1
+    assert 0 < info.top_wide_nodes <= info.wide_nodes
     tasks = L.make_tasks(48, 32, 24, SEED)
     bufs, res = dev.render_tasks(tasks)
+    sch = dev.last_schedule()
+    assert (sch.schedule, sch.fused, sch.units_in_flight, sch.task_groups) == (2, 0, 4, 2)
     obufs, ores, _ = O.render_tasks(sc.desc(), cam.desc, tasks, O.WAVEFRONT, oracle_threads(), accel=1)
     _tiles_cmp(bufs, res, obufs, ores)
 
@@ -162,8 +167,13 @@ def test_wide_bistro_standin_tiles(dev):
     sc = scenes.bistro(bistro_standin(groups=40, lamps=64, n=4))
     cam = scenes.bistro_camera((48, 32))
     dev.upload(sc, cam)
+    info = dev.scene_info()
+    assert info.accel == 1 and info.n_shadow > 1
+    assert info.lds_bytes == 0 and info.top_bytes > 0 and info.top_wide_nodes > 0  # the TOP kernels
     tasks = L.make_tasks(48, 32, 8, SEED)
     bufs, res = dev.render_tasks(tasks)
+    sch = dev.last_schedule()
+    assert (sch.schedule, sch.fused, sch.units_in_flight, sch.task_groups) == (2, 0, 4, 2)
     obufs, ores, _ = O.render_tasks(sc.desc(), cam.desc, tasks, O.WAVEFRONT, oracle_threads(), accel=1)
     _tiles_cmp(bufs, res, obufs, ores)
 
@@ -273,6 +283,10 @@ def test_wide_texture_zoo(dev):
     assert info.accel == 1 and info.full_kernels == 2
     tasks = L.make_tasks(48, 32, 8, SEED)
     bufs, res = dev.render_tasks(tasks)
+    # the zoo fits the staging limit, so the automatic choice is the fused bounce (feature class 2 has
+    # no LDS variant: its kernels read the scene from HBM) in the fused pipeline
+    sch = dev.last_schedule()
+    assert info.lds_bytes > 0 and info.n_shadow == 1 and (sch.schedule, sch.fused) == (1, 1)
     obufs, ores, _ = O.render_tasks(zoo.desc(), cam.desc, tasks, O.WAVEFRONT, oracle_threads(), accel=1)
     _tiles_cmp(bufs, res, obufs, ores)
     tasks = L.make_tasks(48, 32, 4, SEED)

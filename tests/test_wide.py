@@ -20,7 +20,7 @@ import lumo_amd as L
 import oracle_ffi as O
 from lumo_amd import scenes
 from lumo_amd.procedural import torus_knot_tube
-from scenes import EDGE_SCENES, material_zoo
+from scenes import EDGE_SCENES, DeepLightScene, knot_light_scene, light_kd_depth, material_zoo
 from test_gpu_scale import _arrays, _closest_rays, _visibility_rays
 from test_instances_lights import light_scene, sphere_scene
 
@@ -178,6 +178,38 @@ def test_wide_matches_lumo_except_kd_misses(name):
     o, dirs, li = _visibility_rays(d, 1 << 15, 22)
     a, b, same = _compare(d, o, dirs, li)
     assert (~same).mean() <= BOUND, (~same).mean()
+
+
+def test_light_kd_depth_limit():
+    """wbvh::build refuses a scene with a light kd tree deeper than wbvh::LIGHT_KD_STACK = 16 levels (the
+    root counted as level 1), and the upload then keeps lumo's structures.  The two scenes the GPU test
+    of the refusal uploads (tests/test_gpu_wide_forms.py test_wide_refusal_and_boundary): 16 levels, the
+    last accepted depth, and 17.
+
+    A search over torus_knot_tube light meshes finds no such scene, at any size: the builder turns a
+    light mesh into one triangle light per face (Scene::add_mesh), which has no kd tree, so the only
+    lights with one are rectangles (one leaf of two triangles; asserted below so that a builder that
+    starts keeping light meshes whole shows up here).  DeepLightScene therefore deepens a rectangle
+    light's tree in the scene description itself."""
+    for n, m in ((8, 4), (25, 4), (60, 6), (100, 8), (300, 12)):
+        d = knot_light_scene(n, m).build().desc()
+        assert d.num_lights == d.num_triangles == 2 * n * m and light_kd_depth(d) == 0
+        assert O.wide_export(d)["ok"]
+    assert light_kd_depth(L.Scene.cornell_box().desc()) == 1
+    for levels, ok in ((15, True), (16, True), (17, False), (20, False)):
+        d = DeepLightScene(levels).desc()
+        assert light_kd_depth(d) == levels
+        assert O.wide_export(d)["ok"] == ok, levels
+    # the deepened tree is a kd tree of the same rectangle: the same visibility, whichever structure
+    # the other objects are walked through
+    sc = DeepLightScene(16)
+    o, dirs, li = _visibility_rays(sc.desc(), 1 << 13, 7)
+    base = O.trace(sc._base.desc(), o, dirs, li)
+    for accel in (0, 1):
+        deep = O.trace(sc.desc(), o, dirs, li, accel=accel)
+        np.testing.assert_array_equal(deep[0], base[0])
+        np.testing.assert_array_equal(deep[1], base[1])
+    assert 0.5 < np.mean(base[1] == 2) < 1.0
 
 
 def _image(bufs, tasks, W, H):

@@ -496,6 +496,73 @@ lumo_status lumo_debug_stream(void* ctx, size_t n);
  * of n host uint32 counts into out (n = 0: nothing is written). */
 lumo_status lumo_debug_scan(void* ctx, const uint32_t* in, uint32_t* out, size_t n);
 
+/* ---------------------------------------------------------------------------------
+ * Feature buffers: the first hit's albedo, shading normal and depth of every film sample, for
+ * denoisers and compositing.  An addition within ABI 10: no existing layout changes, so the
+ * capability check is the presence of these two symbols (dlsym), not the version.
+ *
+ * A feature render takes the same tasks, sampler and seeds as lumo_render_tiles and is aligned
+ * with its film sample for sample: sample (task, pass, pixel) has the beauty sample's raster
+ * position, lens point and wavelengths, lands in the planes with the beauty film's filter weights
+ * summed in the same order, and channel 3 of every plane is the beauty tile's sum w bit for bit.
+ * The camera ray's Scene::hit (scene.rs:119-147) gives the record; nothing is followed through
+ * mirrors or glass.  Per sample:
+ *   kind, object, prim   as lumo_trace: 0 miss, 1 object, 2 light; index; global triangle or -1
+ *   material, backface   the hit's material index (-1 on a miss), Hit::backface (hit.rs:37-59)
+ *   t, p, ng, uv         the hit record (uv wrapped; the ray is normalised, so t is a distance)
+ *   ns                   the shading normal with the bump map applied (material.rs:323-331)
+ *   n                    backface ? -ns : ns (the normal feature)
+ *   albedo               at the sample's 4 wavelengths: kd of Lambertian / MfDiffuse, ks of
+ *                        MfConductor, tf of MfDielectric, 1 for a light, 0 for Blank
+ *   albedo_rgb           albedo through the film's spectrum -> XYZ -> white balance -> RGB,
+ *                        without a tone map
+ * All are 0 on a miss (material -1, object and prim -1).
+ * ------------------------------------------------------------------------------- */
+/* Filtered planes of one task: caller-allocated, 4 doubles per tile pixel laid out as rgb_w; a
+ * NULL plane is skipped.  A miss contributes its weight with zero features.
+ *   albedo_w   sum w albedo_rgb, sum w
+ *   normal_w   sum w n, sum w
+ *   depth_w    sum w t hit, sum w hit, 0, sum w   (hit = 1 when kind != 0): depth is channel 0
+ *              over channel 1, coverage channel 1 over channel 3 */
+typedef struct {
+    double* albedo_w;
+    double* normal_w;
+    double* depth_w;
+} lumo_feature_planes;
+typedef struct {
+    int32_t sampler;   /* LUMO_SAMPLER_* */
+    int32_t max_paths; /* cap on paths in flight (0 = all pixels of the call), as lumo_render_cfg */
+} lumo_feature_cfg;
+/* Per-sample records of one task: arrays sized samples x pixels, pass-major, pixels in raster
+ * order within the tile (as lumo_path_dump); the number after each name is its doubles / ints per
+ * sample.  A NULL array is skipped. */
+typedef struct {
+    int32_t* kind;       /* 1 */
+    int32_t* object;     /* 1 */
+    int32_t* prim;       /* 1 */
+    int32_t* material;   /* 1 */
+    int32_t* backface;   /* 1 */
+    double* t;           /* 1 */
+    double* p;           /* 3 */
+    double* ng;          /* 3 */
+    double* ns;          /* 3 */
+    double* n;           /* 3 */
+    double* uv;          /* 2 */
+    double* albedo;      /* 4 */
+    double* albedo_rgb;  /* 3 */
+    double* raster;      /* 2 */
+    double* lambda_;     /* 4 */
+} lumo_feature_dump;
+/* The feature planes of n tasks (cfg NULL: MultiJittered, no cap), chunked by max_paths as
+ * lumo_render_tiles.  Serves both integrators (the camera path is the same).  Errors as
+ * lumo_render_tiles: LUMO_ERR_INVALID (NULL context, tasks or out, a malformed task, an unknown
+ * sampler, Sobol with more than 1023 samples), LUMO_ERR_NO_SCENE, LUMO_ERR_NO_CAMERA.  Leaves
+ * lumo_last_schedule's record as it is. */
+lumo_status lumo_render_features(void* ctx, const lumo_tile_task* tasks, size_t n, const lumo_feature_cfg* cfg,
+                                 lumo_feature_planes* out);
+/* Test hook: the per-sample records of one task, with the sampler of lumo_debug_set_sampler. */
+lumo_status lumo_debug_features(void* ctx, const lumo_tile_task* task, lumo_feature_dump* dump);
+
 #ifdef __cplusplus
 }
 #endif

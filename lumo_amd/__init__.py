@@ -18,7 +18,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import check
 
-__all__ = ["Spectrum", "Texture", "NormalMap", "Material", "Scene", "Camera", "Renderer", "Integrator", "ToneMap", "Film", "Device",
+__all__ = ["Spectrum", "Texture", "NormalMap", "Material", "Scene", "Camera", "Renderer", "Integrator", "ToneMap", "Film", "FeatureFilm", "Device",
            "DENSE", "TILE_SIZE", "SAMPLES_INCREMENT", "make_tasks"]
 
 TILE_SIZE = 16          # renderer.rs:15
@@ -697,6 +697,60 @@ class Film:
         write_png(path, self.rgb_image())
 
 
+class FeatureFilm:
+    """The feature planes of a frame (lumo_render_features): per pixel the filtered sums of the
+    first hit's albedo (RGB), oriented shading normal and depth, 4 doubles each as Film.pixels."""
+
+    def __init__(self, width, height, color_space=1):
+        self.width, self.height = width, height
+        self.color_space = color_space
+        self.albedo_w = np.zeros((height, width, 4), dtype=np.float64)  # Σw·albedo_rgb, Σw
+        self.normal_w = np.zeros((height, width, 4), dtype=np.float64)  # Σw·n, Σw
+        self.depth_w = np.zeros((height, width, 4), dtype=np.float64)   # Σw·t·hit, Σw·hit, 0, Σw
+
+    def add_tile(self, task, planes):
+        """Adds one task's (albedo_w, normal_w, depth_w) arrays; batches of a tile accumulate."""
+        x0, y0 = task.px_min[0], task.px_min[1]
+        x1, y1 = task.px_max[0], task.px_max[1]
+        for dst, src in zip((self.albedo_w, self.normal_w, self.depth_w), planes):
+            dst[y0:y1, x0:x1, :] += np.asarray(src, dtype=np.float64).reshape(y1 - y0, x1 - x0, 4)
+
+    @staticmethod
+    def _ratio(num, den):
+        """num / den, 0 where den is 0 (an empty pixel is 0, not NaN)."""
+        den = np.broadcast_to(den, num.shape)
+        out = np.zeros(num.shape, dtype=np.float64)
+        np.divide(num, den, out=out, where=den != 0.0)
+        return out
+
+    def albedo(self):
+        """H x W x 3: Σw·albedo_rgb / Σw."""
+        return self._ratio(self.albedo_w[..., :3], self.albedo_w[..., 3:4])
+
+    def normal(self):
+        """H x W x 3: Σw·n renormalised to unit length; 0 where nothing was hit."""
+        n = self.normal_w[..., :3]
+        return self._ratio(n, np.sqrt((n * n).sum(axis=-1, keepdims=True)))
+
+    def depth(self):
+        """H x W: the mean distance of the samples that hit, Σw·t·hit / Σw·hit."""
+        return self._ratio(self.depth_w[..., 0], self.depth_w[..., 1])
+
+    def coverage(self):
+        """H x W: the share of the pixel's filter weight that hit something, Σw·hit / Σw."""
+        return self._ratio(self.depth_w[..., 1], self.depth_w[..., 3])
+
+    def save_albedo(self, path):
+        """8-bit RGB PNG of the albedo, encoded like the film."""
+        from .image import encode, write_png
+        write_png(path, encode(self.albedo(), self.color_space))
+
+    def save_normal(self, path):
+        """8-bit RGB PNG of 0.5 n + 0.5 (linear); empty pixels are mid grey."""
+        from .image import _as_u8, write_png
+        write_png(path, _as_u8(255.0 * (0.5 * self.normal() + 0.5) + 0.5))
+
+
 class Device:
     """One lumo_amd context bound to one GPU (lumo_create)."""
 
@@ -782,6 +836,41 @@ class Device:
                      np.zeros(0, dtype=[("x", "<u4"), ("y", "<u4"), ("rgb", "<f8", (3,))]))
                 splats_out.append(a.copy())
         return bufs, res
+
+    def render_features(self, tasks, max_paths=0, sampler=0):
+        """lumo_render_features over `tasks`: per task the (albedo_w, normal_w, depth_w) planes,
+        each a flat array of 4 f64 per tile pixel, aligned sample for sample with render_tasks of
+        the same tasks and sampler (channel 3 of every plane is that tile's Σw)."""
+        L = lib()
+        n = len(tasks)
+        arr = tasks if isinstance(tasks, C.Array) else (_ffi.TileTask * n)(*tasks)
+        out = (_ffi.FeaturePlanes * n)()
+        planes = []
+        if n:  # each plane's tiles back to back in one allocation, as _result_buffers lays out rgb_w
+            ov = np.frombuffer(out, dtype=np.uint64).reshape(n, 3)
+            for k in range(3):
+                bufs, _, res = self._result_buffers(arr, n)
+                ov[:, k] = np.frombuffer(res, dtype=np.uint64).reshape(n, -1)[:, 0]
+                planes.append(bufs)
+        cfg = _ffi.FeatureCfg(int(sampler), int(max_paths))
+        check(L.lumo_render_features(self.ctx, arr, n, C.byref(cfg), out), "render_features")
+        return list(zip(*planes))
+
+    def debug_features(self, task, sampler=0):
+        """lumo_debug_features: the per-sample feature records of one task as a dict of
+        (samples x pixels, k) arrays (pass-major, pixels in raster order; "lambda_" the
+        wavelengths), with pixel sampler `sampler` (set through lumo_debug_set_sampler for the call)."""
+        L = lib()
+        m = (task.px_max[0] - task.px_min[0]) * (task.px_max[1] - task.px_min[1]) * task.samples
+        bufs = {name: np.zeros((m, k) if k > 1 else m, dtype=dt) for name, dt, k in _ffi.FEATURE_DUMP_FIELDS}
+        dump = _ffi.FeatureDump(*(bufs[name].ctypes.data_as(_ffi.c_int32_p if dt == "i4" else _ffi.c_double_p)
+                                  for name, dt, _ in _ffi.FEATURE_DUMP_FIELDS))
+        check(L.lumo_debug_set_sampler(self.ctx, int(sampler)), "debug_set_sampler")
+        try:
+            check(L.lumo_debug_features(self.ctx, C.byref(task), C.byref(dump)), "debug_features")
+        finally:
+            L.lumo_debug_set_sampler(self.ctx, 0)
+        return bufs
 
     def trace(self, origins, dirs, lights=None):
         """lumo_trace: closest hit (Scene::hit, scene.rs:119-147) of each ray, or with `lights`
@@ -942,5 +1031,23 @@ class Renderer:
             self.num_rays += sum(r.num_rays for r in res)
             self.num_camera_rays += sum(r.num_camera_rays for r in res)
             self.tasks_rendered += len(mine)
+        dev.close()
+        return film
+
+    def render_features(self, rank=0, world_size=1):
+        """The feature planes (FeatureFilm) of the frame render() renders with the same seed, samples
+        and sampler, sample for sample; with world_size > 1 this rank's tiles of the static shard
+        (tile_index % world_size == rank).  One call serves both integrators."""
+        if self._seed is None:
+            raise ValueError("Renderer.render_features: set .seed() (the seed of the render it goes with)")
+        w, h = self.camera.resolution
+        tasks = make_tasks(w, h, self._samples, self._seed)
+        from .dist import shard_tasks
+        mine = shard_tasks(tasks, w, h, rank, world_size)
+        dev = Device(self._device)
+        dev.upload(self.scene, self.camera)
+        film = FeatureFilm(w, h, getattr(self.camera, "color_space", 1))
+        for t, planes in zip(mine, dev.render_features(mine, sampler=self._sampler)):
+            film.add_tile(t, planes)
         dev.close()
         return film

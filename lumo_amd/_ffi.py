@@ -195,6 +195,25 @@ class PathDump(C.Structure):
                 ("depth", c_uint64_p), ("delta", c_double_p)]
 
 
+class FeaturePlanes(C.Structure):
+    _fields_ = [("albedo_w", c_double_p), ("normal_w", c_double_p), ("depth_w", c_double_p)]
+
+
+class FeatureCfg(C.Structure):
+    _fields_ = [("sampler", C.c_int32), ("max_paths", C.c_int32)]
+
+
+# lumo_feature_dump: (field, numpy dtype, values per sample), in the struct's order
+FEATURE_DUMP_FIELDS = [("kind", "i4", 1), ("object", "i4", 1), ("prim", "i4", 1), ("material", "i4", 1),
+                       ("backface", "i4", 1), ("t", "f8", 1), ("p", "f8", 3), ("ng", "f8", 3), ("ns", "f8", 3),
+                       ("n", "f8", 3), ("uv", "f8", 2), ("albedo", "f8", 4), ("albedo_rgb", "f8", 3),
+                       ("raster", "f8", 2), ("lambda_", "f8", 4)]
+
+
+class FeatureDump(C.Structure):
+    _fields_ = [(name, c_int32_p if dt == "i4" else c_double_p) for name, dt, _ in FEATURE_DUMP_FIELDS]
+
+
 # (name, restype, argtypes) of every exported symbol declared in include/*.h
 DEVICE_API = [
     ("lumo_create", C.c_int32, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -220,6 +239,9 @@ DEVICE_API = [
     ("lumo_debug_set_sampler", C.c_int32, [C.c_void_p, C.c_int]),
     ("lumo_debug_trace", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.c_int, C.c_int, c_double_p, C.POINTER(C.c_int)]),
     ("lumo_debug_paths", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.POINTER(PathDump)]),
+    ("lumo_render_features", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.c_size_t, C.POINTER(FeatureCfg),
+                                         C.POINTER(FeaturePlanes)]),
+    ("lumo_debug_features", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.POINTER(FeatureDump)]),
 ]
 HOST_API = [
     ("lumo_spectrum_from_rgb", Spectrum, [C.c_double, C.c_double, C.c_double]),

@@ -701,6 +701,8 @@ __global__ __launch_bounds__(64) void k_ring(DScene sc, Paths S, Tasks T, int n_
     }
 }
 
+// ------------------------------------------------------------------ feature buffers (lumo_render_features)
+#include "features.h"
 
 // ------------------------------------------------------------------ BDPT splats -> film taps
 // FilmTile::add_sample with splat = true (film/tile.rs:65-111): tone map, XYZ, white balance,
@@ -812,6 +814,7 @@ enum WorkId {
     W_BD_FILM, W_BD_REDO_INDEX, W_BD_NL, W_BD_NC, W_BD_NITEMS, W_BD_IOFF, W_BD_DRAWS, W_BD_OK, W_BD_ITOTAL, W_BD_PDF,
     W_BD_WDEPTH, W_BD_CAMO, W_BD_CAMD, W_BD_RNG0, W_BD_LAM0, W_BD_NB, W_BD_OFFB,
     W_CHECKS, W_BD_LM, W_BD_LMF, W_BD_CM, W_BD_CMF,
+    W_FT_ALB, W_FT_NRM, W_FT_DEP, W_FT_FILM_A, W_FT_FILM_N, W_FT_FILM_D, W_FT_DUMP_I, W_FT_DUMP_D,
     W_SET0,  // pass set k's field f: W_SET0 + k * F_SET_COUNT + f
     W_COUNT = W_SET0 + 4 * F_SET_COUNT
 };
@@ -1072,6 +1075,7 @@ struct Render {
     size_t film_n = 0;
     std::vector<uint64_t> n_splats;
     uint64_t bounces = 0;  // bounces that ran paths, from the count snapshots
+    bool features = false;  // a feature render (render_features_impl): camera paths only, no NEE records
 };
 
 // Count snapshots of a chain of bounces.  Bounces are enqueued ahead of the host's knowledge of the
@@ -2104,7 +2108,7 @@ lumo_status alloc_render(Ctx& c, Render& R) {
     const size_t NV = (size_t)N * (size_t)plan.M;
     const size_t cap = plan.schedule == LUMO_SCHED_FUSED_PIPELINE ? (size_t)N : NV;
     Paths& S = R.P[0];
-    alloc_pass_set(c, S, 0, bdpt ? SET_OUT : SET_ALL, NV, cap, st);
+    alloc_pass_set(c, S, 0, bdpt ? SET_OUT : (R.features ? SET_OUT | SET_QUEUES : SET_ALL), NV, cap, st);
     // per slot: camera sampler, raster, final values; BDPT also its walk state
     S.task = wbuf<int32_t>(c, W_TASK, N, st);
     S.pix = wbuf<int32_t>(c, W_PIX, N, st);
@@ -2359,6 +2363,146 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
     return read_back(c, R);
 }
 
+// A feature render (features.h): render_impl's steps 1, 3 and 4 (slots, work buffers, setup on
+// stream 0), then per pass on stream 0 the camera, one closest-hit launch over its queue (queue 0,
+// no ray sort), k_features and the pass's share of the three planes.  It plans no schedule and
+// leaves the record of lumo_last_schedule alone.  The camera rays count as closest queries with the
+// traversal counters of class 0.
+constexpr int FT_DUMP_DOUBLES = 28;  // t 1, p 3, ng 3, ns 3, n 3, uv 2, albedo 4, albedo_rgb 3, raster 2, lambda 4
+lumo_status render_features_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lumo_feature_planes* out,
+                                 const lumo_feature_dump* dump) {
+    if (!c.has_scene) return LUMO_ERR_NO_SCENE;
+    if (!c.has_camera) return LUMO_ERR_NO_CAMERA;
+    if (n_tasks == 0) return LUMO_OK;
+    Render R{tasks, n_tasks, nullptr, nullptr, 0};
+    R.features = true;
+    lumo_status st = build_slots(R);
+    if (st) return st;
+    R.plan = SchedPlan{LUMO_SCHED_SEQUENTIAL, false, 1, 1, 1, 0, 0, 0};
+    if ((st = alloc_render(c, R))) return st;
+    const int N = R.N, n_t = (int)n_tasks;
+    Paths& S = R.P[0];
+    S.hq = HitQ{wbuf<double>(c, W_SET0 + F_HQ_T, N, st), wbuf<int32_t>(c, W_SET0 + F_HQ_I, 3 * (size_t)N, st),
+                (size_t)N, nullptr, nullptr, nullptr, nullptr};
+    Feat F{};
+    F.alb = wbuf<double>(c, W_FT_ALB, 3 * (size_t)N, st);
+    F.nrm = wbuf<double>(c, W_FT_NRM, 3 * (size_t)N, st);
+    F.dep = wbuf<double>(c, W_FT_DEP, 2 * (size_t)N, st);
+    F.film_a = wbuf<double>(c, W_FT_FILM_A, 4 * (size_t)N, st);
+    F.film_n = wbuf<double>(c, W_FT_FILM_N, 4 * (size_t)N, st);
+    F.film_d = wbuf<double>(c, W_FT_FILM_D, 4 * (size_t)N, st);
+    const size_t m = dump ? (size_t)tasks[0].samples * (size_t)N : 0;  // a dump: one task
+    int32_t* di = nullptr;
+    double* dd = nullptr;
+    if (dump) {
+        di = wbuf<int32_t>(c, W_FT_DUMP_I, 5 * m, st);
+        dd = wbuf<double>(c, W_FT_DUMP_D, FT_DUMP_DOUBLES * m, st);
+        F.d = FeatDump{di, di + m, di + 2 * m, di + 3 * m, di + 4 * m,
+                       dd, dd + m, dd + 4 * m, dd + 7 * m, dd + 10 * m, dd + 13 * m, dd + 15 * m, dd + 19 * m,
+                       dd + 22 * m, dd + 24 * m};
+        F.dump_p = N;
+    }
+    if (st) return st;
+    if ((st = setup_render(c, R))) return st;
+    hipStream_t sm = c.streams[0];
+    {
+        ZeroList z;
+        z.add(F.film_a, sizeof(double) * 4 * N);
+        z.add(F.film_n, sizeof(double) * 4 * N);
+        z.add(F.film_d, sizeof(double) * 4 * N);
+        k_zero_list<<<std::min(ceil_div((uint64_t)4 * N, BLOCK), 2048), BLOCK, 0, sm>>>(z);
+    }
+    const int gN = ceil_div(N, BLOCK);
+    for (uint64_t pass = 0; pass < R.max_samples; ++pass) {
+        {   // S.counts: zeroed at setup, then at the end of every pass
+            StageTimer tm(c, c.o.timing, ST_CAMERA, sm);
+            k_camera<true><<<gN, BLOCK, 0, sm>>>(R.T, S, c.cam, N, R.dim_stride, (uint32_t)pass, 0, 1, 0);
+        }
+        k_bounce_begin<<<1, 64, 0, sm>>>(S.counts, S.tcount + TC_HEADQ);
+        {
+            StageTimer tm(c, c.o.timing, ST_CLOSEST, sm);
+            launch_trav(
+                c, (uint64_t)N,
+                [&](auto K, const TravLaunch& l) { launch_closest_q<decltype(K)::value>(l, c.sc, S, S.qs[0], 0u); }, sm,
+                true);
+        }
+        {
+            StageTimer tm(c, c.o.timing, ST_SHADE, sm);
+            by_fx(c.sc.full, [&](auto FX) {
+                k_features<decltype(FX)::value><<<gN, BLOCK, 0, sm>>>(c.sc, S, F, c.cam, S.qs[0], (uint32_t)pass);
+            });
+        }
+        {
+            StageTimer tm(c, c.o.timing, ST_FILM, sm);
+            if (R.max_P <= BLOCK)
+                k_feature_film<<<n_t, BLOCK, 0, sm>>>(S, F, R.T, c.cam, 0);
+            else
+                k_feature_gather<<<gN, BLOCK, 0, sm>>>(S, F, R.T, c.cam, N);
+        }
+        k_zero_counts<<<1, 64, 0, sm>>>(S.counts, nullptr);
+        HIPCHK(hipGetLastError());
+        if (c.o.timing) resolve_timers(c);
+    }
+    // the planes: straight into the caller's buffers when they lie back to back in slot order
+    const double* films[3] = {F.film_a, F.film_n, F.film_d};
+    std::vector<double> host;
+    for (int k = 0; k < 3 && out; ++k) {
+        auto plane = [&](size_t i) { return k == 0 ? out[i].albedo_w : (k == 1 ? out[i].normal_w : out[i].depth_w); };
+        bool any = false, direct = plane(0) != nullptr;
+        for (size_t i = 0; i < n_tasks; ++i) {
+            any = any || plane(i) != nullptr;
+            direct = direct && plane(i) == plane(0) + 4 * (size_t)R.first[i];
+        }
+        if (!any) continue;
+        if (direct) {
+            HIPCHK(hipMemcpyAsync(plane(0), films[k], sizeof(double) * 4 * N, hipMemcpyDeviceToHost, sm));
+            continue;
+        }
+        host.resize((size_t)4 * N);
+        HIPCHK(hipMemcpyAsync(host.data(), films[k], sizeof(double) * 4 * N, hipMemcpyDeviceToHost, sm));
+        HIPCHK(hipStreamSynchronize(sm));
+        for (size_t i = 0; i < n_tasks; ++i)
+            if (plane(i))
+                std::memcpy(plane(i), host.data() + 4 * (size_t)R.first[i],
+                            sizeof(double) * 4 * (size_t)(R.first[i + 1] - R.first[i]));
+    }
+    if (dump) {
+        int32_t* const hi[5] = {dump->kind, dump->object, dump->prim, dump->material, dump->backface};
+        double* const hd[10] = {dump->t, dump->p, dump->ng, dump->ns, dump->n, dump->uv, dump->albedo, dump->albedo_rgb,
+                                dump->raster, dump->lambda_};
+        const int per[10] = {1, 3, 3, 3, 3, 2, 4, 3, 2, 4};
+        for (int k = 0; k < 5; ++k)
+            if (hi[k]) HIPCHK(hipMemcpyAsync(hi[k], di + k * m, sizeof(int32_t) * m, hipMemcpyDeviceToHost, sm));
+        size_t o = 0;
+        for (int k = 0; k < 10; ++k) {
+            if (hd[k]) HIPCHK(hipMemcpyAsync(hd[k], dd + o * m, sizeof(double) * per[k] * m, hipMemcpyDeviceToHost, sm));
+            o += (size_t)per[k];
+        }
+    }
+    unsigned long long tc[TC_ALL];
+    HIPCHK(hipMemcpyAsync(tc, S.tcount, sizeof(tc), hipMemcpyDeviceToHost, sm));
+    HIPCHK(hipStreamSynchronize(sm));
+    if (c.o.timing) resolve_timers(c);
+    c.stats.closest_queries += tc[TC_HEADQ];
+    c.stats.aabb_tests[0] += tc[TC_AABB];
+    c.stats.kd_nodes[0] += tc[TC_KD];
+    c.stats.tri_tests[0] += tc[TC_TRI];
+    return LUMO_OK;
+}
+
+// The task list of a call cut so that at most max_paths slots are in flight (lumo_render_tiles'
+// chunking): the end of the chunk that starts at task i.
+size_t chunk_end(const lumo_tile_task* tasks, size_t n, size_t i, size_t max_paths) {
+    size_t j = i, paths = 0;
+    while (j < n) {
+        const size_t P = (tasks[j].px_max[0] - tasks[j].px_min[0]) * (tasks[j].px_max[1] - tasks[j].px_min[1]);
+        if (j > i && paths + P > max_paths) break;
+        paths += P;
+        ++j;
+    }
+    return j;
+}
+
 }  // namespace
 
 // ================================================================== C ABI
@@ -2544,6 +2688,41 @@ lumo_status lumo_debug_paths(void* ctx, const lumo_tile_task* task, lumo_path_du
     c->sampler = c->debug_sampler;
     const lumo_status st = render_impl(*c, task, 1, nullptr, &D, task->samples);
     c->integrator = LUMO_INTEGRATOR_PATH_TRACE;
+    c->sampler = LUMO_SAMPLER_MULTI_JITTERED;
+    return st;
+}
+
+// Feature planes of n tasks (features.h); the sampler applies to this call only.
+lumo_status lumo_render_features(void* ctx, const lumo_tile_task* tasks, size_t n, const lumo_feature_cfg* cfg,
+                                 lumo_feature_planes* out) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || (!tasks && n) || (!out && n)) return LUMO_ERR_INVALID;
+    const int sampler = cfg ? cfg->sampler : LUMO_SAMPLER_MULTI_JITTERED;
+    if (sampler < LUMO_SAMPLER_MULTI_JITTERED || sampler > LUMO_SAMPLER_SOBOL) return LUMO_ERR_INVALID;
+    for (size_t i = 0; i < n && sampler == LUMO_SAMPLER_SOBOL; ++i)
+        if (tasks[i].total_samples > 1023) return LUMO_ERR_INVALID;  // sobol_seq.rs SOBOL_MAX_LEN (lumo panics)
+    HIPCHK(hipSetDevice(c->device));
+    const size_t max_paths = (cfg && cfg->max_paths > 0) ? (size_t)cfg->max_paths : (size_t)1 << 30;
+    c->sampler = sampler;
+    lumo_status st = LUMO_OK;
+    if (n == 0) st = render_features_impl(*c, tasks, 0, out, nullptr);  // the scene and camera checks
+    for (size_t i = 0; i < n && !st;) {
+        const size_t j = chunk_end(tasks, n, i, max_paths);
+        st = render_features_impl(*c, tasks + i, j - i, out + i, nullptr);
+        i = j;
+    }
+    c->sampler = LUMO_SAMPLER_MULTI_JITTERED;
+    return st;
+}
+
+// Test hook: the per-sample feature records of one task, with lumo_debug_set_sampler's sampler.
+lumo_status lumo_debug_features(void* ctx, const lumo_tile_task* task, lumo_feature_dump* dump) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !task || !dump) return LUMO_ERR_INVALID;
+    if (c->debug_sampler == LUMO_SAMPLER_SOBOL && task->total_samples > 1023) return LUMO_ERR_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    c->sampler = c->debug_sampler;
+    const lumo_status st = render_features_impl(*c, task, 1, nullptr, dump);
     c->sampler = LUMO_SAMPLER_MULTI_JITTERED;
     return st;
 }

@@ -17,11 +17,13 @@ BUILD    ?= build
 HOST_OBJ := $(patsubst lumo_amd/csrc/host/%.cpp,build/host/%.o,$(HOST_SRC))
 # kernels.hip: the non-traversal kernels, the schedulers and the entry points that launch them;
 # ctx.hip (context, options) and upload.hip (scene, camera) are host code only and share ctx.h with
-# it.  The traversal kernels are instantiated once per kd stack class (launch.h STACK_CLASSES) in
+# it; denoise.hip is the denoiser (denoise.h's kernels and lumo_denoise).  The traversal kernels are instantiated once per kd stack class (launch.h STACK_CLASSES) in
 # their own translation units, so they compile in parallel: inst_pt.hip / inst_bd.hip built with
 # -DLUMO_STK=<class>.
 STK_CLASSES := 0 4 8 16 24 32 48 64
-MAIN_OBJ := $(BUILD)/device/kernels.o $(BUILD)/device/ctx.o $(BUILD)/device/upload.o
+MAIN_OBJ := $(BUILD)/device/kernels.o $(BUILD)/device/ctx.o $(BUILD)/device/upload.o $(BUILD)/device/denoise.o
+# denoise.hip is all f64: compiled without the packed f32 instructions
+FLAGS_denoise := -Xclang -target-feature -Xclang -packed-fp32-ops
 DEV_OBJ  := $(MAIN_OBJ) $(foreach k,$(STK_CLASSES),$(BUILD)/device/inst_pt_$(k).o $(BUILD)/device/inst_bd_$(k).o)
 CTX_H    := lumo_amd/csrc/device/ctx.h lumo_amd/csrc/host/wbvh.h
 DEV_H    := $(filter-out $(CTX_H),$(wildcard lumo_amd/csrc/device/*.h))
@@ -39,7 +41,7 @@ build/host/%.o: lumo_amd/csrc/host/%.cpp $(COMMON_H) $(wildcard lumo_amd/csrc/ho
 
 $(MAIN_OBJ): $(BUILD)/device/%.o: lumo_amd/csrc/device/%.hip $(COMMON_H) $(DEV_H) $(CTX_H)
 	@mkdir -p $(BUILD)/device
-	$(HIPCC) $(HIPFLAGS) $(DEVFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(DEVFLAGS) $(FLAGS_$*) -c $< -o $@
 
 $(BUILD)/device/inst_pt_%.o: lumo_amd/csrc/device/inst_pt.hip $(COMMON_H) $(DEV_H)
 	@mkdir -p $(BUILD)/device

@@ -563,6 +563,72 @@ lumo_status lumo_render_features(void* ctx, const lumo_tile_task* tasks, size_t 
 /* Test hook: the per-sample records of one task, with the sampler of lumo_debug_set_sampler. */
 lumo_status lumo_debug_features(void* ctx, const lumo_tile_task* task, lumo_feature_dump* dump);
 
+/* ---------------------------------------------------------------------------------
+ * Denoiser: an edge-avoiding a-trous wavelet filter guided by the feature planes, with albedo
+ * demodulation and a spatial variance estimate (the spatial part of SVGF).  An addition within
+ * ABI 10: the capability check is the presence of lumo_denoise (dlsym).
+ *
+ * Inputs and outputs are host arrays of a whole frame, height x width, row-major: the film's
+ * rgb_w and the three feature planes as lumo_render_tiles / lumo_render_features produce them
+ * (4 doubles per pixel), and optionally add_rgb (3 per pixel), added to the colour after the
+ * division by sum w (BDPT: splat_scale * splats / filter integral).  All arithmetic is f64 in the
+ * order below, never contracted; exp is lm_exp (common/lmath.h); max(x, f) is x > f ? x : f and
+ * min(x, f) is x < f ? x : f; a sum starts at 0.0 and adds its taps in row-major order (dy outer,
+ * dx inner, ascending); a tap outside the image is skipped unless a step says clamped.
+ *   1 prepare   c = rgb_w[0..2] / rgb_w[3] (0 when rgb_w[3] = 0), + add_rgb;
+ *               cov = depth_w[1] / depth_w[3], z = depth_w[0] / depth_w[1] (each 0 when its
+ *               denominator is 0); hit = cov > 0; n = normal_w[0..2] / sqrt((x x + y y) + z z) (0
+ *               when that is 0); a = albedo_w[0..2] / albedo_w[3] (0 when albedo_w[3] = 0);
+ *               a' = max(a + (1 - cov), albedo_floor) when demodulate, else 1; e = c / a';
+ *               l = (0.2126 e0 + 0.7152 e1) + 0.0722 e2;
+ *               fz = max(|z(x+1, y) - z|, |z(x, y+1) - z|), coordinates clamped
+ *   2 pair      centre p, tap q at pixel offset (ox, oy): neither a hit: wn = 1, dz = 0; exactly
+ *               one a hit: the tap's weight is 0; else d = max((nx nx' + ny ny') + nz nz', 0),
+ *               wn = d squared k times, dz = |z_p - z_q| / ((sigma_z fz_p) sqrt(ox ox + oy oy) +
+ *               depth_floor z_p)
+ *   3 variance  the (2r+1)^2 window at unit stride, the centre with weight 1, the others with
+ *               w = wn exp(-min(dz, 700)): m1 = sum(w l) / sum w, m2 = sum(w (l l)) / sum w,
+ *               var = max(m2 - m1 m1, 0)
+ *   4 a-trous   iteration i = 0 .. N-1, step s = 2^i: gv = the 3 x 3 binomial (1/4 1/2 1/4 per
+ *               axis) of var at unit stride, clamped; taps at (s dx, s dy), dx, dy in -2 .. 2,
+ *               h = b[dy+2] b[dx+2], b = (1/16, 1/4, 3/8, 1/4, 1/16); the centre's weight is h, the
+ *               others' w = (h wn) exp(-min(dz + dl, 700)), dl = |l_p - l_q| / (sigma_l sqrt(gv) +
+ *               lum_floor); e' = sum(w e) / sum w, var' = sum((w w) var) / (sum w sum w); l from e'
+ *   5 finish    rgb_out = e a'; variance_out = var
+ * Non-finite inputs give unspecified values around them.  The guides are the first hit's, so a
+ * reflection or refraction is filtered with the guides of the surface it is seen in.
+ * ------------------------------------------------------------------------------- */
+typedef struct {
+    int64_t width, height;
+    const double* rgb_w;    /* 4 per pixel: sum w rgb, sum w */
+    const double* albedo_w; /* lumo_feature_planes, assembled into the frame */
+    const double* normal_w;
+    const double* depth_w;
+    const double* add_rgb;  /* 3 per pixel, or NULL */
+} lumo_denoise_in;
+typedef struct {
+    int32_t iterations;        /* N: 1 .. 5 (default 5) */
+    int32_t normal_log2_power; /* k: 0 .. 10 (default 7: the normals' dot product to the 128th) */
+    int32_t variance_radius;   /* r: 1 .. 3 (default 3) */
+    int32_t demodulate;        /* 0 / 1 (default 1) */
+    double sigma_l;            /* default 4.0 */
+    double sigma_z;            /* default 1.0 */
+    double albedo_floor;       /* default 1e-3 */
+    double depth_floor;        /* default 1e-3 */
+    double lum_floor;          /* default 1e-8 */
+    double* stage_ms;          /* NULL, or N + 5 doubles: the call's device times in ms (HIP events) of the
+                                  upload, prepare, variance, each a-trous iteration, finish, the read-back */
+} lumo_denoise_cfg;
+/* lumo_denoise(void* ctx, const lumo_denoise_in* in, const lumo_denoise_cfg* cfg, double* rgb_out,
+ * double* variance_out): the denoised linear RGB frame into rgb_out (3 doubles per pixel) and, when
+ * variance_out is not NULL, the filtered variance of the demodulated luminance (1 per pixel).  cfg
+ * NULL: the defaults.  LUMO_ERR_INVALID for a NULL context, in or rgb_out, a NULL plane among the
+ * four, a width or height below 1 (or above 2^20), a cfg field outside its range or a non-finite
+ * one; LUMO_ERR_OOM as elsewhere.  Needs no scene or camera; runs on the main stream, returns after
+ * the read-back and leaves the stats and lumo_last_schedule's record alone. */
+lumo_status lumo_denoise(void* ctx, const lumo_denoise_in* in, const lumo_denoise_cfg* cfg, double* rgb_out,
+                         double* variance_out);
+
 #ifdef __cplusplus
 }
 #endif

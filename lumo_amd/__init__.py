@@ -18,7 +18,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import check
 
-__all__ = ["Spectrum", "Texture", "NormalMap", "Material", "Scene", "Camera", "Renderer", "Integrator", "ToneMap", "Film", "FeatureFilm", "Device",
+__all__ = ["Spectrum", "Texture", "NormalMap", "Material", "Scene", "Camera", "Renderer", "Integrator", "ToneMap", "Film", "FeatureFilm", "DenoisedFilm", "Device",
            "DENSE", "TILE_SIZE", "SAMPLES_INCREMENT", "make_tasks"]
 
 TILE_SIZE = 16          # renderer.rs:15
@@ -751,6 +751,28 @@ class FeatureFilm:
         write_png(path, _as_u8(255.0 * (0.5 * self.normal() + 0.5) + 0.5))
 
 
+class DenoisedFilm:
+    """A denoised frame (Device.denoise): H x W x 3 linear RGB with the film's colour space."""
+
+    def __init__(self, pixels, color_space=1, variance=None):
+        self.pixels = pixels
+        self.height, self.width = pixels.shape[:2]
+        self.color_space = color_space
+        self.variance = variance  # H x W, with return_variance
+
+    def rgb(self):
+        return self.pixels
+
+    def rgb_image(self):
+        """Encoded 8-bit RGB, rows top to bottom, as Film.rgb_image."""
+        from .image import encode
+        return encode(self.rgb(), self.color_space)
+
+    def save(self, path):
+        from .image import write_png
+        write_png(path, self.rgb_image())
+
+
 class Device:
     """One lumo_amd context bound to one GPU (lumo_create)."""
 
@@ -871,6 +893,38 @@ class Device:
         finally:
             L.lumo_debug_set_sampler(self.ctx, 0)
         return bufs
+
+    def denoise(self, film, features, return_variance=False, stage_ms=None, **cfg):
+        """lumo_denoise: the edge-avoiding a-trous filter of `film` (a Film) guided by `features`
+        (the FeatureFilm of the same frame), as an H x W x 3 float64 array of linear RGB, what
+        Film.rgb() covers: the light-tracing splats of a BDPT film go in as add_rgb.  `cfg`: fields
+        of lumo_denoise_cfg (iterations, sigma_l, sigma_z, normal_log2_power, variance_radius,
+        demodulate, albedo_floor, depth_floor, lum_floor); return_variance: also the filtered
+        variance (H x W); stage_ms: a list that receives the call's device times (upload, prepare,
+        variance, each iteration, finish, read-back).  Needs no uploaded scene.  Multi-GPU: reduce
+        the films and the feature films to one rank, then call this there."""
+        h, w = film.pixels.shape[:2]
+        if features.albedo_w.shape[:2] != (h, w):
+            raise ValueError(f"denoise: film is {w} x {h}, features are {features.width} x {features.height}")
+        unknown = set(cfg) - set(_ffi.DENOISE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"denoise: unknown cfg field(s) {sorted(unknown)}")
+        planes = [np.ascontiguousarray(a, dtype=np.float64)
+                  for a in (film.pixels, features.albedo_w, features.normal_w, features.depth_w)]
+        add = None
+        if film.splats.any():
+            add = np.ascontiguousarray(film.splat_scale * film.splats / film.filter_integral())
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_ffi.c_double_p)  # noqa: E731
+        args = _ffi.DenoiseIn(w, h, *(ptr(a) for a in planes), ptr(add))
+        c = _ffi.DenoiseCfg(**{**_ffi.DENOISE_DEFAULTS, **cfg})
+        times = np.zeros(c.iterations + 5) if stage_ms is not None else None
+        c.stage_ms = ptr(times)
+        out = np.zeros((h, w, 3))
+        var = np.zeros((h, w)) if return_variance else None
+        check(lib().lumo_denoise(self.ctx, C.byref(args), C.byref(c), ptr(out), ptr(var)), "denoise")
+        if times is not None:
+            stage_ms.extend(times.tolist())
+        return (out, var) if return_variance else out
 
     def trace(self, origins, dirs, lights=None):
         """lumo_trace: closest hit (Scene::hit, scene.rs:119-147) of each ray, or with `lights`
@@ -1051,3 +1105,25 @@ class Renderer:
             film.add_tile(t, planes)
         dev.close()
         return film
+
+    def render_denoised(self, **cfg):
+        """(film, features, denoised): render() and render_features() of the frame with the renderer's
+        seed (set .seed(), as render_features asks), then Device.denoise of the two with `cfg`
+        (lumo_denoise_cfg's fields) as a DenoisedFilm.  The filter works on linear radiance: a tone
+        map set on the renderer is not applied to the render it filters.  Single-rank; with several
+        GPUs render the shards, reduce the films and the feature films to one rank and call
+        Device.denoise there."""
+        if self._seed is None:
+            raise ValueError("Renderer.render_denoised: set .seed()")
+        tone, self._tone_map = self._tone_map, ToneMap.NO_MAP
+        try:
+            film = self.render()
+        finally:
+            self._tone_map = tone
+        features = self.render_features()
+        dev = Device(self._device)
+        try:
+            out = dev.denoise(film, features, **cfg)
+        finally:
+            dev.close()
+        return film, features, DenoisedFilm(out, film.color_space)

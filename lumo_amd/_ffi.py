@@ -203,6 +203,23 @@ class FeatureCfg(C.Structure):
     _fields_ = [("sampler", C.c_int32), ("max_paths", C.c_int32)]
 
 
+class DenoiseIn(C.Structure):
+    _fields_ = [("width", C.c_int64), ("height", C.c_int64), ("rgb_w", c_double_p), ("albedo_w", c_double_p),
+                ("normal_w", c_double_p), ("depth_w", c_double_p), ("add_rgb", c_double_p)]
+
+
+class DenoiseCfg(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("normal_log2_power", C.c_int32), ("variance_radius", C.c_int32),
+                ("demodulate", C.c_int32), ("sigma_l", C.c_double), ("sigma_z", C.c_double),
+                ("albedo_floor", C.c_double), ("depth_floor", C.c_double), ("lum_floor", C.c_double),
+                ("stage_ms", c_double_p)]
+
+
+# lumo_denoise_cfg's defaults (a NULL cfg), by field
+DENOISE_DEFAULTS = dict(iterations=5, normal_log2_power=7, variance_radius=3, demodulate=1, sigma_l=4.0, sigma_z=1.0,
+                        albedo_floor=1e-3, depth_floor=1e-3, lum_floor=1e-8)
+
+
 # lumo_feature_dump: (field, numpy dtype, values per sample), in the struct's order
 FEATURE_DUMP_FIELDS = [("kind", "i4", 1), ("object", "i4", 1), ("prim", "i4", 1), ("material", "i4", 1),
                        ("backface", "i4", 1), ("t", "f8", 1), ("p", "f8", 3), ("ng", "f8", 3), ("ns", "f8", 3),
@@ -242,6 +259,7 @@ DEVICE_API = [
     ("lumo_render_features", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.c_size_t, C.POINTER(FeatureCfg),
                                          C.POINTER(FeaturePlanes)]),
     ("lumo_debug_features", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.POINTER(FeatureDump)]),
+    ("lumo_denoise", C.c_int32, [C.c_void_p, C.POINTER(DenoiseIn), C.POINTER(DenoiseCfg), c_double_p, c_double_p]),
 ]
 HOST_API = [
     ("lumo_spectrum_from_rgb", Spectrum, [C.c_double, C.c_double, C.c_double]),

@@ -119,6 +119,7 @@ struct Ctx {
     DCam cam{};
     std::vector<DevBuf> scene_bufs;
     std::vector<DevBuf> work;  // grown on demand
+    std::vector<DevBuf> dn_work;  // lumo_denoise (denoise.hip), grown on demand
     lumo_stats stats{};
     lumo_schedule_info sched{};  // of the last render
     Timing tm;

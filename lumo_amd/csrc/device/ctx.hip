@@ -285,6 +285,8 @@ void lumo_destroy(void* ctx) {
     free_scene(*c);
     for (DevBuf& b : c->work)
         if (b.p) (void)hipFree(b.p);
+    for (DevBuf& b : c->dn_work)
+        if (b.p) (void)hipFree(b.p);
     for (DevBuf& b : c->gwork)
         if (b.p) (void)hipFree(b.p);
     for (int i = 0; i < Ctx::SNAP_RING; ++i) (void)hipEventDestroy(c->snap_ev[i]);

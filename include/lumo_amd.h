@@ -565,8 +565,9 @@ lumo_status lumo_debug_features(void* ctx, const lumo_tile_task* task, lumo_feat
 
 /* ---------------------------------------------------------------------------------
  * Denoiser: an edge-avoiding a-trous wavelet filter guided by the feature planes, with albedo
- * demodulation and a spatial variance estimate (the spatial part of SVGF).  An addition within
- * ABI 10: the capability check is the presence of lumo_denoise (dlsym).
+ * demodulation and a spatial variance estimate (the spatial part of SVGF; lumo_denoise_temporal
+ * below is the temporal part).  An addition within ABI 10: the capability check is the presence
+ * of lumo_denoise (dlsym).
  *
  * Inputs and outputs are host arrays of a whole frame, height x width, row-major: the film's
  * rgb_w and the three feature planes as lumo_render_tiles / lumo_render_features produce them
@@ -628,6 +629,89 @@ typedef struct {
  * the read-back and leaves the stats and lumo_last_schedule's record alone. */
 lumo_status lumo_denoise(void* ctx, const lumo_denoise_in* in, const lumo_denoise_cfg* cfg, double* rgb_out,
                          double* variance_out);
+
+/* ---------------------------------------------------------------------------------
+ * Temporal denoiser: the other half of SVGF.  The previous call's colour and luminance moments
+ * are reprojected through the depth and normal guides and accumulated per pixel, the accumulated
+ * moments give the variance that drives the a-trous edge stops where the history is long enough,
+ * and one a-trous iteration's output is fed back as the next call's colour history.  An addition
+ * within ABI 10: the capability check is the presence of lumo_denoise_temporal (dlsym).
+ *
+ * The context keeps the history of its last lumo_denoise_temporal call on the device: per pixel
+ * the colour history e (3), the luminance moments m1, m2, the history length (an integer), the
+ * guides n (3), z and hit, and with them that call's camera.  lumo_denoise_reset drops it, and so
+ * does a call with another width or height; lumo_destroy frees it.  A call without history is a
+ * first frame and equals lumo_denoise of the same input bit for bit.  lumo_denoise neither reads
+ * nor writes the history.
+ *
+ * The rules are lumo_denoise's: f64, never contracted, exp = lm_exp, max(x, f) = x > f ? x : f,
+ * min likewise, sums from 0.0 in row-major order.  xf(T, p) is the point transform of T's matrix
+ * (row r: ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 w, then the division by w unless w = 0), xf_inv that
+ * of its inverse, with w = 1 for a point and 0 for a direction; normalize(a) = a / sqrt(max((ax ax +
+ * ay ay) + az az, 0)) (common/vec.h).  Primed names belong to the previous call.
+ *   1 prepare     step 1 of lumo_denoise: e, l, n, z, hit, a', fz
+ *   2 position    a hit pixel (x, y): the camera ray of raster point (x + 0.5, y + 0.5) with lens
+ *                 radius 0, as k_camera computes it: s = xf_inv(screen_to_raster, (x + 0.5, y + 0.5,
+ *                 0)), c = xf_inv(camera_to_screen, s), o = xf_inv(world_to_camera, (0, 0, 0)),
+ *                 d = normalize(xf_inv(world_to_camera, normalize(c)) as a direction);
+ *                 P = o + z d per component.  A pixel that is not a hit has no history.
+ *   3 previous    c' = xf(world_to_camera', P); no history unless c'.z > 0 (the view axis is +z in
+ *     raster      camera space); q = xf(screen_to_raster', xf(camera_to_screen', c')); no history
+ *                 unless qx and qy are finite; o' = xf_inv(world_to_camera', (0, 0, 0)),
+ *                 z' = sqrt(max(|P - o'|^2, 0)) with the squared length summed as in normalize
+ *   4 taps        u = qx - 0.5, v = qy - 0.5, x0 = floor(u), y0 = floor(v), fx = u - x0, fy = v - y0
+ *                 (a q more than 2 pixels outside the image has no tap inside it: no history).
+ *                 Taps (x0 + i, y0 + j), i, j in 0 .. 1, i inner, with w = ((1 - fx) | fx) ((1 - fy)
+ *                 | fy).  A tap is valid when it lies inside the image, was a hit, (nx nx' + ny ny')
+ *                 + nz nz' >= normal_cos_min and |z_tap - z'| <= depth_rel_max z'.  Over the valid
+ *                 taps, sum w > 0: the history of e0, e1, e2, m1, m2 is sum(w h) / sum w and the
+ *                 history length the largest valid tap's.  Else the 3 x 3 taps around (floor(u +
+ *                 0.5), floor(v + 0.5)), w = 1 each, the same test; none valid: no history.
+ *   5 accumulate  with history: N = min(len + 1, max_history), al = max(alpha, 1 / N),
+ *                 x_acc = (1 - al) x_hist + al x for e0..2, for m1 from l and for m2 from l l;
+ *                 without: N = 1, e_acc = e, m1 = l, m2 = l l
+ *   6 variance    N >= min_history: var = max(m2 - m1 m1, 0); elsewhere step 3 of lumo_denoise
+ *                 with l the luminance of e_acc
+ *   7 a-trous     steps 4 and 5 of lumo_denoise on e_acc and var.  The e' of iteration
+ *                 feedback - 1 (e_acc when feedback = 0) becomes the colour history; m1, m2, N, n,
+ *                 z, hit and the camera are stored with it.
+ * The guides are the first hit's (as lumo_denoise), a miss keeps no history, and a thin lens is
+ * treated as a pinhole: the depth of a lens sample is a distance from its lens point, so P is
+ * approximate there.
+ * ------------------------------------------------------------------------------- */
+typedef struct {
+    double alpha;           /* 0 .. 1 (default 0.2): blend floor for colour and moments */
+    double normal_cos_min;  /* -1 .. 1 (default 0.9): a history tap's normal agrees to this cosine */
+    double depth_rel_max;   /* 0 .. 1e6 (default 0.1): a history tap's depth agrees to this fraction */
+    int32_t max_history;    /* 1 .. 1024 (default 32): cap on the history length */
+    int32_t min_history;    /* 1 .. 1025 (default 4): history length from which the temporal variance is used */
+    int32_t feedback;       /* 0 .. cfg's iterations (default 1): the a-trous iteration whose output becomes
+                               the colour history; 0: the unfiltered accumulated colour */
+    int32_t stage_lds;      /* 0 / 1 (default 1): 0 forces the direct-gather form of k_dn_reproject; no
+                               result depends on it */
+} lumo_temporal_cfg;
+typedef struct {
+    int64_t with_history;    /* pixels whose reprojection found history */
+    int64_t without_history; /* the others: width x height - with_history */
+    int64_t blocks_staged;   /* k_dn_reproject blocks that tapped the history from their LDS tile */
+    int64_t blocks_direct;   /* blocks that tapped it from global memory; a block none of whose pixels has a
+                                tap to read (a first frame, a camera turned away) is in neither count */
+    double* stage_ms;        /* NULL, or N + 8 doubles: the call's device times in ms (HIP events) in launch
+                                order: upload, prepare, reproject, variance, the variance choice, the N
+                                iterations with the history write in its place (first when feedback = 0,
+                                else after iteration feedback - 1), finish, the read-back.  Set it before
+                                the call; cfg's stage_ms is not used */
+} lumo_temporal_info;
+/* lumo_denoise_temporal: lumo_denoise's arguments, the frame's camera, tcfg (NULL: the defaults) and
+ * info (NULL, or filled in).  Errors as lumo_denoise, and LUMO_ERR_INVALID for a NULL camera, a camera
+ * whose width or height differs from in's, a tcfg field outside its range or a non-finite one;
+ * LUMO_ERR_UNSUPPORTED for an orthographic camera (its depth is not a distance from one point).  A
+ * call that fails leaves no history.  A steady-state call uploads what lumo_denoise uploads. */
+lumo_status lumo_denoise_temporal(void* ctx, const lumo_denoise_in* in, const lumo_camera_desc* camera,
+                                  const lumo_denoise_cfg* cfg, const lumo_temporal_cfg* tcfg, double* rgb_out,
+                                  double* variance_out, lumo_temporal_info* info);
+/* Drops the context's history: the next lumo_denoise_temporal call is a first frame. */
+lumo_status lumo_denoise_reset(void* ctx);
 
 #ifdef __cplusplus
 }

@@ -751,6 +751,10 @@ class FeatureFilm:
         write_png(path, _as_u8(255.0 * (0.5 * self.normal() + 0.5) + 0.5))
 
 
+def _dptr(a):
+    return None if a is None else a.ctypes.data_as(_ffi.c_double_p)
+
+
 class DenoisedFilm:
     """A denoised frame (Device.denoise): H x W x 3 linear RGB with the film's colour space."""
 
@@ -903,28 +907,58 @@ class Device:
         variance (H x W); stage_ms: a list that receives the call's device times (upload, prepare,
         variance, each iteration, finish, read-back).  Needs no uploaded scene.  Multi-GPU: reduce
         the films and the feature films to one rank, then call this there."""
-        h, w = film.pixels.shape[:2]
-        if features.albedo_w.shape[:2] != (h, w):
-            raise ValueError(f"denoise: film is {w} x {h}, features are {features.width} x {features.height}")
-        unknown = set(cfg) - set(_ffi.DENOISE_DEFAULTS)
-        if unknown:
-            raise TypeError(f"denoise: unknown cfg field(s) {sorted(unknown)}")
-        planes = [np.ascontiguousarray(a, dtype=np.float64)
-                  for a in (film.pixels, features.albedo_w, features.normal_w, features.depth_w)]
-        add = None
-        if film.splats.any():
-            add = np.ascontiguousarray(film.splat_scale * film.splats / film.filter_integral())
-        ptr = lambda a: None if a is None else a.ctypes.data_as(_ffi.c_double_p)  # noqa: E731
-        args = _ffi.DenoiseIn(w, h, *(ptr(a) for a in planes), ptr(add))
+        args, keep, (h, w) = self._denoise_in("denoise", film, features, cfg, _ffi.DENOISE_DEFAULTS)
         c = _ffi.DenoiseCfg(**{**_ffi.DENOISE_DEFAULTS, **cfg})
         times = np.zeros(c.iterations + 5) if stage_ms is not None else None
-        c.stage_ms = ptr(times)
+        c.stage_ms = _dptr(times)
         out = np.zeros((h, w, 3))
         var = np.zeros((h, w)) if return_variance else None
-        check(lib().lumo_denoise(self.ctx, C.byref(args), C.byref(c), ptr(out), ptr(var)), "denoise")
+        check(lib().lumo_denoise(self.ctx, C.byref(args), C.byref(c), _dptr(out), _dptr(var)), "denoise")
         if times is not None:
             stage_ms.extend(times.tolist())
         return (out, var) if return_variance else out
+
+    @staticmethod
+    def _denoise_in(what, film, features, cfg, known):
+        """(lumo_denoise_in of the frame, the arrays it points into, (h, w)); raises for cfg fields not in `known`."""
+        h, w = film.pixels.shape[:2]
+        if features.albedo_w.shape[:2] != (h, w):
+            raise ValueError(f"{what}: film is {w} x {h}, features are {features.width} x {features.height}")
+        unknown = set(cfg) - set(known)
+        if unknown:
+            raise TypeError(f"{what}: unknown cfg field(s) {sorted(unknown)}")
+        keep = [np.ascontiguousarray(a, dtype=np.float64)
+                for a in (film.pixels, features.albedo_w, features.normal_w, features.depth_w)]
+        keep.append(np.ascontiguousarray(film.splat_scale * film.splats / film.filter_integral())
+                    if film.splats.any() else None)
+        return _ffi.DenoiseIn(w, h, *(_dptr(a) for a in keep)), keep, (h, w)
+
+    def denoise_temporal(self, film, features, camera, return_variance=False, info=None, **cfg):
+        """lumo_denoise_temporal: Device.denoise with the context's history of its previous call
+        reprojected through `camera` (the frame's Camera) and accumulated; the first
+        call, and the first after denoise_reset() or a change of size, equals Device.denoise.  `cfg`:
+        fields of lumo_denoise_cfg and of lumo_temporal_cfg (alpha, max_history, min_history,
+        normal_cos_min, depth_rel_max, feedback, stage_lds) by name.  info: a dict that receives
+        with_history, without_history, blocks_staged, blocks_direct and stage_ms (the call's device
+        times: upload, prepare, reproject, variance, the variance choice, the iterations with the
+        history write in its place, finish, read-back)."""
+        args, keep, (h, w) = self._denoise_in("denoise_temporal", film, features, cfg,
+                                              {**_ffi.DENOISE_DEFAULTS, **_ffi.TEMPORAL_DEFAULTS})
+        pick = lambda d: {**d, **{k: v for k, v in cfg.items() if k in d}}  # noqa: E731
+        c, t = _ffi.DenoiseCfg(**pick(_ffi.DENOISE_DEFAULTS)), _ffi.TemporalCfg(**pick(_ffi.TEMPORAL_DEFAULTS))
+        times = np.zeros(c.iterations + 8) if info is not None else None
+        ti = _ffi.TemporalInfo(stage_ms=_dptr(times))
+        out = np.zeros((h, w, 3))
+        var = np.zeros((h, w)) if return_variance else None
+        check(lib().lumo_denoise_temporal(self.ctx, C.byref(args), C.byref(camera.desc), C.byref(c), C.byref(t), _dptr(out),
+                                          _dptr(var), C.byref(ti)), "denoise_temporal")
+        if info is not None:
+            info.update({k: getattr(ti, k) for k, _ in _ffi.TemporalInfo._fields_[:4]}, stage_ms=times.tolist())
+        return (out, var) if return_variance else out
+
+    def denoise_reset(self):
+        """lumo_denoise_reset: drops the history; the next denoise_temporal call is a first frame."""
+        check(lib().lumo_denoise_reset(self.ctx), "denoise_reset")
 
     def trace(self, origins, dirs, lights=None):
         """lumo_trace: closest hit (Scene::hit, scene.rs:119-147) of each ray, or with `lights`
@@ -1127,3 +1161,27 @@ class Renderer:
         finally:
             dev.close()
         return film, features, DenoisedFilm(out, film.color_space)
+
+    def render_denoised_sequence(self, cameras, **cfg):
+        """Yields (film, features, denoised) per camera of `cameras` (each with the renderer's camera's
+        resolution): render_denoised's frame with that camera, denoised by Device.denoise_temporal on
+        one context whose history is reset at the start, so frame k accumulates frames 0 .. k - 1.
+        Frame k is rendered with seed (seed + k) mod 2^64 of the renderer's .seed(), which must be
+        set.  `cfg`: the fields Device.denoise_temporal takes.  The renderer's own camera and seed
+        are as before afterwards."""
+        if self._seed is None:
+            raise ValueError("Renderer.render_denoised_sequence: set .seed()")
+        seed, camera, tone = self._seed, self.camera, self._tone_map
+        dev = Device(self._device)
+        try:
+            dev.denoise_reset()
+            for k, cam in enumerate(cameras):
+                self._seed, self.camera, self._tone_map = (seed + k) & 0xFFFFFFFFFFFFFFFF, cam, ToneMap.NO_MAP
+                film = self.render()
+                features = self.render_features()
+                out = dev.denoise_temporal(film, features, cam, **cfg)
+                self._seed, self.camera, self._tone_map = seed, camera, tone
+                yield film, features, DenoisedFilm(out, film.color_space)
+        finally:
+            self._seed, self.camera, self._tone_map = seed, camera, tone
+            dev.close()

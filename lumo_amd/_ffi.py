@@ -220,6 +220,21 @@ DENOISE_DEFAULTS = dict(iterations=5, normal_log2_power=7, variance_radius=3, de
                         albedo_floor=1e-3, depth_floor=1e-3, lum_floor=1e-8)
 
 
+class TemporalCfg(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("normal_cos_min", C.c_double), ("depth_rel_max", C.c_double),
+                ("max_history", C.c_int32), ("min_history", C.c_int32), ("feedback", C.c_int32), ("stage_lds", C.c_int32)]
+
+
+class TemporalInfo(C.Structure):
+    _fields_ = [("with_history", C.c_int64), ("without_history", C.c_int64), ("blocks_staged", C.c_int64),
+                ("blocks_direct", C.c_int64), ("stage_ms", c_double_p)]
+
+
+# lumo_temporal_cfg's defaults (a NULL tcfg), by field
+TEMPORAL_DEFAULTS = dict(alpha=0.2, normal_cos_min=0.9, depth_rel_max=0.1, max_history=32, min_history=4, feedback=1,
+                         stage_lds=1)
+
+
 # lumo_feature_dump: (field, numpy dtype, values per sample), in the struct's order
 FEATURE_DUMP_FIELDS = [("kind", "i4", 1), ("object", "i4", 1), ("prim", "i4", 1), ("material", "i4", 1),
                        ("backface", "i4", 1), ("t", "f8", 1), ("p", "f8", 3), ("ng", "f8", 3), ("ns", "f8", 3),
@@ -260,6 +275,9 @@ DEVICE_API = [
                                          C.POINTER(FeaturePlanes)]),
     ("lumo_debug_features", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.POINTER(FeatureDump)]),
     ("lumo_denoise", C.c_int32, [C.c_void_p, C.POINTER(DenoiseIn), C.POINTER(DenoiseCfg), c_double_p, c_double_p]),
+    ("lumo_denoise_temporal", C.c_int32, [C.c_void_p, C.POINTER(DenoiseIn), C.POINTER(CameraDesc), C.POINTER(DenoiseCfg),
+                                          C.POINTER(TemporalCfg), c_double_p, c_double_p, C.POINTER(TemporalInfo)]),
+    ("lumo_denoise_reset", C.c_int32, [C.c_void_p]),
 ]
 HOST_API = [
     ("lumo_spectrum_from_rgb", Spectrum, [C.c_double, C.c_double, C.c_double]),

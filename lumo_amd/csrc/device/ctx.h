@@ -120,6 +120,12 @@ struct Ctx {
     std::vector<DevBuf> scene_bufs;
     std::vector<DevBuf> work;  // grown on demand
     std::vector<DevBuf> dn_work;  // lumo_denoise (denoise.hip), grown on demand
+    // lumo_denoise_temporal's history (denoise.hip): two sets of planes, read from dn_hist_set and
+    // written to the other, the counters of a call, and the frame and camera the history belongs to
+    DevBuf dn_hist[2], dn_hist_cnt;
+    int dn_hist_set = 0;
+    int64_t dn_hist_w = 0, dn_hist_h = 0;  // 0: no history
+    lumo_camera_desc dn_hist_cam{};
     lumo_stats stats{};
     lumo_schedule_info sched{};  // of the last render
     Timing tm;

@@ -287,6 +287,8 @@ void lumo_destroy(void* ctx) {
         if (b.p) (void)hipFree(b.p);
     for (DevBuf& b : c->dn_work)
         if (b.p) (void)hipFree(b.p);
+    for (DevBuf* b : {&c->dn_hist[0], &c->dn_hist[1], &c->dn_hist_cnt})
+        if (b->p) (void)hipFree(b->p);
     for (DevBuf& b : c->gwork)
         if (b.p) (void)hipFree(b.p);
     for (int i = 0; i < Ctx::SNAP_RING; ++i) (void)hipEventDestroy(c->snap_ev[i]);

@@ -1,13 +1,15 @@
-// lumo_denoise: the entry point of the denoiser (device/denoise.h).  It uploads a
-// frame's beauty film and feature planes, runs prepare, the variance estimate, the a-trous
-// iterations and finish on the context's main stream, and reads the result back.  It needs no
-// scene or camera and touches neither the stats nor the schedule record.
+// lumo_denoise and lumo_denoise_temporal: the entry points of the denoiser (device/denoise.h,
+// DESIGN.md §4d; device/denoise_temporal.h, §4e).  A call uploads a frame's beauty film and feature
+// planes, runs prepare, (the reprojection of the context's history,) the variance estimate, the
+// a-trous iterations and finish on the context's main stream, and reads the result back.  Neither
+// needs a scene or touches the stats or the schedule record.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "ctx.h"
 #include "denoise.h"
+#include "denoise_temporal.h"
 
 using namespace lumo;
 using namespace lumo::dev;
@@ -29,7 +31,7 @@ bool cfg_valid(const lumo_denoise_cfg& g) {
 struct DnClock {
     hipStream_t sm;
     bool on;
-    hipEvent_t ev[DN_MAX_ITER + 6] = {};
+    hipEvent_t ev[DN_MAX_ITER + 9] = {};  // lumo_denoise_temporal marks N + 9 times
     int n = 0;
     DnClock(hipStream_t s, bool enable) : sm(s), on(enable) {}
     void mark() {
@@ -49,29 +51,44 @@ struct DnClock {
     }
 };
 
-}  // namespace
-
-extern "C" lumo_status lumo_denoise(void* ctx, const lumo_denoise_in* in, const lumo_denoise_cfg* cfg, double* rgb_out,
-                                    double* variance_out) {
-    Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c || !in || !rgb_out || !in->rgb_w || !in->albedo_w || !in->normal_w || !in->depth_w) return LUMO_ERR_INVALID;
-    if (in->width < 1 || in->height < 1 || in->width > (1 << 20) || in->height > (1 << 20)) return LUMO_ERR_INVALID;
-    lumo_denoise_cfg g = {5, 7, 3, 1, 4.0, 1.0, 1e-3, 1e-3, 1e-8, nullptr};
-    if (cfg) g = *cfg;
-    if (!cfg_valid(g)) return LUMO_ERR_INVALID;
-    HIPCHK(hipSetDevice(c->device));
-    const int W = (int)in->width, H = (int)in->height;
-    const size_t n = (size_t)W * H;
-    if (c->dn_work.size() < DN_BUF_COUNT) c->dn_work.resize(DN_BUF_COUNT);
-    const size_t bytes[DN_BUF_COUNT] = {32 * n, 32 * n, 32 * n, 32 * n, in->add_rgb ? 24 * n : 0,
-                                        sizeof(double) * DN_NPLANES * n, sizeof(uint32_t) * n, 24 * n};
-    for (int k = 0; k < DN_BUF_COUNT; ++k) {
-        const lumo_status st = dev_alloc(*c, c->dn_work[k], bytes[k]);
-        if (st) return st;
-    }
-    auto buf = [&](int k) { return static_cast<double*>(c->dn_work[k].p); };
+// What the two entry points share: the checked arguments, the work buffers and the launches.
+struct DnCall {
+    Ctx* c;
+    const lumo_denoise_in* in;
+    lumo_denoise_cfg g;
+    DnCfg dc;
     DnPlanes P;
-    {
+    int W, H;
+    size_t n;
+    size_t bytes[DN_BUF_COUNT];
+    unsigned pix_blocks;
+    hipStream_t sm;
+
+    double* buf(int k) const { return static_cast<double*>(c->dn_work[k].p); }
+
+    lumo_status open(void* ctx, const lumo_denoise_in* in_, const lumo_denoise_cfg* cfg, const double* rgb_out) {
+        c = static_cast<Ctx*>(ctx), in = in_;
+        if (!c || !in || !rgb_out || !in->rgb_w || !in->albedo_w || !in->normal_w || !in->depth_w) return LUMO_ERR_INVALID;
+        if (in->width < 1 || in->height < 1 || in->width > (1 << 20) || in->height > (1 << 20)) return LUMO_ERR_INVALID;
+        g = {5, 7, 3, 1, 4.0, 1.0, 1e-3, 1e-3, 1e-8, nullptr};
+        if (cfg) g = *cfg;
+        if (!cfg_valid(g)) return LUMO_ERR_INVALID;
+        W = (int)in->width, H = (int)in->height;
+        n = (size_t)W * H;
+        dc = DnCfg{g.sigma_l, g.sigma_z, g.albedo_floor, g.depth_floor, g.lum_floor, g.normal_log2_power, g.demodulate};
+        pix_blocks = (unsigned)((n + 255) / 256);
+        sm = c->streams[0];
+        return LUMO_OK;
+    }
+    lumo_status alloc() {
+        if (c->dn_work.size() < DN_BUF_COUNT) c->dn_work.resize(DN_BUF_COUNT);
+        const size_t b[DN_BUF_COUNT] = {32 * n, 32 * n, 32 * n, 32 * n, in->add_rgb ? 24 * n : 0,
+                                        sizeof(double) * DN_NPLANES * n, sizeof(uint32_t) * n, 24 * n};
+        for (int k = 0; k < DN_BUF_COUNT; ++k) {
+            bytes[k] = b[k];
+            const lumo_status st = dev_alloc(*c, c->dn_work[k], bytes[k]);
+            if (st) return st;
+        }
         double* p = buf(DN_PLANES);
         auto take = [&]() { double* q = p; p += n; return q; };
         for (int k = 0; k < 3; ++k) P.n[k] = take();
@@ -83,40 +100,175 @@ extern "C" lumo_status lumo_denoise(void* ctx, const lumo_denoise_in* in, const 
             P.var[set] = take();
         }
         P.hit = static_cast<uint32_t*>(c->dn_work[DN_HIT].p);
+        return LUMO_OK;
     }
-    const DnCfg dc{g.sigma_l, g.sigma_z, g.albedo_floor, g.depth_floor, g.lum_floor, g.normal_log2_power, g.demodulate};
-    hipStream_t sm = c->streams[0];
-    DnClock clk(sm, g.stage_ms != nullptr);
-
-    clk.mark();
-    const double* host[5] = {in->rgb_w, in->albedo_w, in->normal_w, in->depth_w, in->add_rgb};
-    for (int k = 0; k < 5; ++k)
-        if (host[k]) HIPCHK(hipMemcpyAsync(buf(DN_IN_RGB + k), host[k], bytes[DN_IN_RGB + k], hipMemcpyHostToDevice, sm));
-    clk.mark();
-    const unsigned pix_blocks = (unsigned)((n + 255) / 256);
-    k_dn_prepare<<<pix_blocks, 256, 0, sm>>>(buf(DN_IN_RGB), buf(DN_IN_ALB), buf(DN_IN_NRM), buf(DN_IN_DEP),
-                                             in->add_rgb ? buf(DN_IN_ADD) : nullptr, P, dc, W, H);
-    clk.mark();
+    lumo_status upload() const {
+        const double* host[5] = {in->rgb_w, in->albedo_w, in->normal_w, in->depth_w, in->add_rgb};
+        for (int k = 0; k < 5; ++k)
+            if (host[k]) HIPCHK(hipMemcpyAsync(buf(DN_IN_RGB + k), host[k], bytes[DN_IN_RGB + k], hipMemcpyHostToDevice, sm));
+        return LUMO_OK;
+    }
+    void prepare() const {
+        k_dn_prepare<<<pix_blocks, 256, 0, sm>>>(buf(DN_IN_RGB), buf(DN_IN_ALB), buf(DN_IN_NRM), buf(DN_IN_DEP),
+                                                 in->add_rgb ? buf(DN_IN_ADD) : nullptr, P, dc, W, H);
+    }
     // the march kernels: x tiles of DN_BW centres; per residue class mod s, chunks of DN_ROWS rows
-    auto march_grid = [&](int s) {
+    dim3 march_grid(int s) const {
         const int chunks = ((H + s - 1) / s + DN_ROWS - 1) / DN_ROWS;
         return dim3((unsigned)((W + DN_BW - 1) / DN_BW), (unsigned)(s * chunks));
+    }
+    void variance() const {
+        k_dn_variance<<<march_grid(1), DN_BW, DnMarch<DN_VAR_R>::lds_bytes(1, DN_VAR_NV), sm>>>(P, dc, g.variance_radius, W, H);
+    }
+    void atrous(int i, int from) const {
+        const int s = 1 << i;
+        k_dn_atrous<<<march_grid(s), DN_BW, DnMarch<DN_AT_R>::lds_bytes(s, DN_AT_NV), sm>>>(P, dc, from, s, W, H);
+    }
+    void finish(int set) const { k_dn_finish<<<pix_blocks, 256, 0, sm>>>(P, set, buf(DN_OUT), n); }
+    lumo_status read_back(int set, double* rgb_out, double* variance_out) const {
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rgb_out, buf(DN_OUT), 24 * n, hipMemcpyDeviceToHost, sm));
+        if (variance_out) HIPCHK(hipMemcpyAsync(variance_out, P.var[set], sizeof(double) * n, hipMemcpyDeviceToHost, sm));
+        return LUMO_OK;
+    }
+};
+
+bool tcfg_valid(const lumo_temporal_cfg& t, int iterations) {
+    for (double v : {t.alpha, t.normal_cos_min, t.depth_rel_max})
+        if (!std::isfinite(v)) return false;
+    return t.alpha >= 0.0 && t.alpha <= 1.0 && t.normal_cos_min >= -1.0 && t.normal_cos_min <= 1.0 &&
+           t.depth_rel_max >= 0.0 && t.depth_rel_max <= 1e6 && t.max_history >= 1 && t.max_history <= 1024 &&
+           t.min_history >= 1 && t.min_history <= 1025 && t.feedback >= 0 && t.feedback <= iterations &&
+           (t.stage_lds == 0 || t.stage_lds == 1);
+}
+
+// The history planes of one set in its buffer: DT_NV doubles, then the length and the hit flag.
+DtHist hist_planes(const DevBuf& b, size_t n) {
+    DtHist h;
+    double* p = static_cast<double*>(b.p);
+    for (int k = 0; k < DT_NV; ++k) h.v[k] = p + (size_t)k * n;
+    h.len = reinterpret_cast<uint32_t*>(p + (size_t)DT_NV * n);
+    h.hit = h.len + n;
+    return h;
+}
+
+DtCam cam_of(const lumo_camera_desc& d) {
+    auto get = [](const double (&a)[2][16]) {  // as lumo_camera_set
+        Xform x;
+        M4* ms[2] = {&x.m, &x.inv};
+        for (int q = 0; q < 2; ++q) {
+            V4* rows[4] = {&ms[q]->y0, &ms[q]->y1, &ms[q]->y2, &ms[q]->y3};
+            for (int r = 0; r < 4; ++r) *rows[r] = V4{a[q][4 * r], a[q][4 * r + 1], a[q][4 * r + 2], a[q][4 * r + 3]};
+        }
+        return x;
     };
-    k_dn_variance<<<march_grid(1), DN_BW, DnMarch<DN_VAR_R>::lds_bytes(1, DN_VAR_NV), sm>>>(P, dc, g.variance_radius, W, H);
+    return DtCam{get(d.world_to_camera), get(d.screen_to_raster), get(d.camera_to_screen)};
+}
+
+}  // namespace
+
+extern "C" lumo_status lumo_denoise(void* ctx, const lumo_denoise_in* in, const lumo_denoise_cfg* cfg, double* rgb_out,
+                                    double* variance_out) {
+    DnCall k;
+    lumo_status st = k.open(ctx, in, cfg, rgb_out);
+    if (st) return st;
+    HIPCHK(hipSetDevice(k.c->device));
+    if ((st = k.alloc())) return st;
+    DnClock clk(k.sm, k.g.stage_ms != nullptr);
+
+    clk.mark();
+    if ((st = k.upload())) return st;
+    clk.mark();
+    k.prepare();
+    clk.mark();
+    k.variance();
     clk.mark();
     int set = 0;
-    for (int i = 0; i < g.iterations; ++i, set ^= 1) {
-        const int s = 1 << i;
-        k_dn_atrous<<<march_grid(s), DN_BW, DnMarch<DN_AT_R>::lds_bytes(s, DN_AT_NV), sm>>>(P, dc, set, s, W, H);
+    for (int i = 0; i < k.g.iterations; ++i, set ^= 1) {
+        k.atrous(i, set);
         clk.mark();
     }
-    k_dn_finish<<<pix_blocks, 256, 0, sm>>>(P, set, buf(DN_OUT), n);
+    k.finish(set);
     clk.mark();
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(rgb_out, buf(DN_OUT), 24 * n, hipMemcpyDeviceToHost, sm));
-    if (variance_out) HIPCHK(hipMemcpyAsync(variance_out, P.var[set], sizeof(double) * n, hipMemcpyDeviceToHost, sm));
+    if ((st = k.read_back(set, rgb_out, variance_out))) return st;
     clk.mark();
-    HIPCHK(hipStreamSynchronize(sm));
-    if (g.stage_ms) clk.read(g.stage_ms);
+    HIPCHK(hipStreamSynchronize(k.sm));
+    if (k.g.stage_ms) clk.read(k.g.stage_ms);
+    return LUMO_OK;
+}
+
+extern "C" lumo_status lumo_denoise_reset(void* ctx) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c) return LUMO_ERR_INVALID;
+    c->dn_hist_w = c->dn_hist_h = 0;
+    return LUMO_OK;
+}
+
+extern "C" lumo_status lumo_denoise_temporal(void* ctx, const lumo_denoise_in* in, const lumo_camera_desc* camera,
+                                             const lumo_denoise_cfg* cfg, const lumo_temporal_cfg* tcfg, double* rgb_out,
+                                             double* variance_out, lumo_temporal_info* info) {
+    DnCall k;
+    lumo_status st = k.open(ctx, in, cfg, rgb_out);
+    if (st) return st;
+    lumo_temporal_cfg t = {0.2, 0.9, 0.1, 32, 4, 1, 1};
+    if (tcfg) t = *tcfg;
+    if (!camera || camera->width != in->width || camera->height != in->height || !tcfg_valid(t, k.g.iterations))
+        return LUMO_ERR_INVALID;
+    if (camera->orthographic) return LUMO_ERR_UNSUPPORTED;
+    Ctx* c = k.c;
+    HIPCHK(hipSetDevice(c->device));
+    const bool has_prev = c->dn_hist_w == in->width && c->dn_hist_h == in->height;
+    c->dn_hist_w = c->dn_hist_h = 0;  // until this call has written its own: a failed call leaves none
+    if ((st = k.alloc())) return st;
+    const size_t n = k.n;
+    for (DevBuf& b : c->dn_hist)
+        if ((st = dev_alloc(*c, b, (sizeof(double) * DT_NV + 2 * sizeof(uint32_t)) * n))) return st;
+    if ((st = dev_alloc(*c, c->dn_hist_cnt, sizeof(unsigned long long) * DT_CNT_N))) return st;
+    const DtHist prev = hist_planes(c->dn_hist[c->dn_hist_set], n), next = hist_planes(c->dn_hist[c->dn_hist_set ^ 1], n);
+    unsigned long long* cnt = static_cast<unsigned long long*>(c->dn_hist_cnt.p);
+    const DtCfg tc{t.alpha, t.normal_cos_min, t.depth_rel_max, t.max_history, t.min_history, t.stage_lds, has_prev ? 1 : 0};
+    DnClock clk(k.sm, info && info->stage_ms);
+
+    clk.mark();
+    if ((st = k.upload())) return st;
+    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * DT_CNT_N, k.sm));
+    clk.mark();
+    k.prepare();
+    clk.mark();
+    const unsigned tiles = (unsigned)((k.W + DT_BX - 1) / DT_BX) * (unsigned)((k.H + DT_BY - 1) / DT_BY);
+    k_dn_reproject<<<tiles, DT_THREADS, 0, k.sm>>>(k.P, prev, next, cam_of(*camera),
+                                                   cam_of(has_prev ? c->dn_hist_cam : *camera), tc, cnt, k.W, k.H);
+    clk.mark();
+    k.variance();
+    clk.mark();
+    k_dn_tvar<<<k.pix_blocks, 256, 0, k.sm>>>(k.P, next, t.min_history, n);
+    clk.mark();
+    int set = 0;
+    for (int i = 0; i <= k.g.iterations; ++i, set ^= 1) {
+        if (i == t.feedback) {  // set holds e_acc (i = 0) or the output of iteration i - 1
+            k_dn_history<<<k.pix_blocks, 256, 0, k.sm>>>(k.P, set, next, n);
+            clk.mark();
+        }
+        if (i == k.g.iterations) break;
+        k.atrous(i, set);
+        clk.mark();
+    }
+    k.finish(set);
+    clk.mark();
+    if ((st = k.read_back(set, rgb_out, variance_out))) return st;
+    clk.mark();
+    unsigned long long counts[DT_CNT_N] = {};
+    HIPCHK(hipMemcpyAsync(counts, cnt, sizeof(counts), hipMemcpyDeviceToHost, k.sm));
+    HIPCHK(hipStreamSynchronize(k.sm));
+    if (info) {
+        info->with_history = (int64_t)counts[DT_CNT_WITH];
+        info->without_history = (int64_t)counts[DT_CNT_WITHOUT];
+        info->blocks_staged = (int64_t)counts[DT_CNT_STAGED];
+        info->blocks_direct = (int64_t)counts[DT_CNT_DIRECT];
+        if (info->stage_ms) clk.read(info->stage_ms);
+    }
+    c->dn_hist_set ^= 1;
+    c->dn_hist_w = in->width, c->dn_hist_h = in->height;
+    c->dn_hist_cam = *camera;
     return LUMO_OK;
 }

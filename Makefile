@@ -17,7 +17,7 @@ BUILD    ?= build
 HOST_OBJ := $(patsubst lumo_amd/csrc/host/%.cpp,build/host/%.o,$(HOST_SRC))
 # kernels.hip: the non-traversal kernels, the schedulers and the entry points that launch them;
 # ctx.hip (context, options) and upload.hip (scene, camera) are host code only and share ctx.h with
-# it; denoise.hip is the denoiser (the kernels of denoise.h and denoise_temporal.h, lumo_denoise, lumo_denoise_temporal).  The traversal kernels are instantiated once per kd stack class (launch.h STACK_CLASSES) in
+# it; denoise.hip is the denoiser (the kernels of denoise.h, denoise_firefly.h and denoise_temporal.h, lumo_denoise, lumo_denoise_temporal).  The traversal kernels are instantiated once per kd stack class (launch.h STACK_CLASSES) in
 # their own translation units, so they compile in parallel: inst_pt.hip / inst_bd.hip built with
 # -DLUMO_STK=<class>.
 STK_CLASSES := 0 4 8 16 24 32 48 64

@@ -583,7 +583,9 @@ lumo_status lumo_debug_features(void* ctx, const lumo_tile_task* task, lumo_feat
  *               a' = max(a + (1 - cov), albedo_floor) when demodulate, else 1; e = c / a';
  *               l = (0.2126 e0 + 0.7152 e1) + 0.0722 e2;
  *               fz = max(|z(x+1, y) - z|, |z(x, y+1) - z|), coordinates clamped
- *   2 pair      centre p, tap q at pixel offset (ox, oy): neither a hit: wn = 1, dz = 0; exactly
+ *   1b firefly  only when lumo_denoise_set_firefly (below, with the step's definition) has set it:
+ *               e and l of a hit pixel that stands out from its alike neighbours are scaled down
+ *   2 pair     centre p, tap q at pixel offset (ox, oy): neither a hit: wn = 1, dz = 0; exactly
  *               one a hit: the tap's weight is 0; else d = max((nx nx' + ny ny') + nz nz', 0),
  *               wn = d squared k times, dz = |z_p - z_q| / ((sigma_z fz_p) sqrt(ox ox + oy oy) +
  *               depth_floor z_p)
@@ -649,8 +651,8 @@ lumo_status lumo_denoise(void* ctx, const lumo_denoise_in* in, const lumo_denois
  * (row r: ((m_r0 x + m_r1 y) + m_r2 z) + m_r3 w, then the division by w unless w = 0), xf_inv that
  * of its inverse, with w = 1 for a point and 0 for a direction; normalize(a) = a / sqrt(max((ax ax +
  * ay ay) + az az, 0)) (common/vec.h).  Primed names belong to the previous call.
- *   1 prepare     step 1 of lumo_denoise: e, l, n, z, hit, a', fz
- *   2 position    a hit pixel (x, y): the camera ray of raster point (x + 0.5, y + 0.5) with lens
+ *   1 prepare     step 1 of lumo_denoise: e, l, n, z, hit, a', fz; then its step 1b when set
+ *   2 position   a hit pixel (x, y): the camera ray of raster point (x + 0.5, y + 0.5) with lens
  *                 radius 0, as k_camera computes it: s = xf_inv(screen_to_raster, (x + 0.5, y + 0.5,
  *                 0)), c = xf_inv(camera_to_screen, s), o = xf_inv(world_to_camera, (0, 0, 0)),
  *                 d = normalize(xf_inv(world_to_camera, normalize(c)) as a direction);
@@ -712,6 +714,51 @@ lumo_status lumo_denoise_temporal(void* ctx, const lumo_denoise_in* in, const lu
                                   double* variance_out, lumo_temporal_info* info);
 /* Drops the context's history: the next lumo_denoise_temporal call is a first frame. */
 lumo_status lumo_denoise_reset(void* ctx);
+
+/* ---------------------------------------------------------------------------------
+ * Firefly clamp: step 1b of lumo_denoise and of lumo_denoise_temporal.  A hit pixel whose
+ * demodulated luminance exceeds an order statistic of its like-guided neighbours' is scaled down
+ * to it, before the variance, the a-trous and, in the temporal call, the reprojection and the
+ * accumulation see it.  Off unless lumo_denoise_set_firefly has set it: per-context state, as an
+ * execution option is, read by both entry points; a first temporal frame equals lumo_denoise under
+ * one and the same setting.  An addition within ABI 10: the capability check is the presence of
+ * lumo_denoise_set_firefly (dlsym).
+ *
+ * The rules are lumo_denoise's (f64, never contracted, max(x, f) = x > f ? x : f, min likewise).
+ * The step uses step 1's values of all pixels, never a value it has itself changed.  c is step 1's
+ * colour before the demodulation (rgb_w[k] / rgb_w[3], 0 when rgb_w[3] = 0, + add_rgb), a' its
+ * divisor, e, l, n, z and hit its outputs.
+ *   1b firefly   a pixel p that is not a hit is unchanged.  The alike neighbours of a hit p are the
+ *                pixels q != p of the (2R+1)^2 window at unit stride that lie inside the image, are
+ *                hits, and have (nx nx' + ny ny') + nz nz' >= normal_cos_min and |z_q - z_p| <=
+ *                depth_rel_max z_p.  m is their count; m < min_alike: unchanged.  Else v is the
+ *                rank-th largest l_q among them (ties are values), b = gain v, and when l_p > b:
+ *                g = b / l_p, c'_k = c_k g, e_k = c'_k / a'_k, l = (0.2126 e0 + 0.7152 e1) + 0.0722 e2.
+ *                Else (a NaN l_p among it) unchanged.
+ * So the step equals the unchanged definition on a frame whose rgb_w is (c', 1) with no add_rgb.
+ * A miss is never clamped (a small sun seen directly survives); a directly seen emitter of fewer
+ * than rank + 1 pixels on a surface is.  With the clamp on, the `prepare` interval of stage_ms
+ * includes the step.
+ * ------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t radius;         /* R: 1 .. 3 (default 2) */
+    int32_t rank;           /* 1 .. 8 (default 2) */
+    int32_t min_alike;      /* rank .. 48 (default 4) */
+    int32_t reserved;       /* 0 */
+    double gain;            /* 1 .. 1e6 (default 1.0) */
+    double normal_cos_min;  /* -1 .. 1 (default 0.9) */
+    double depth_rel_max;   /* 0 .. 1e6 (default 0.1) */
+} lumo_firefly_cfg;
+typedef struct {
+    int64_t clamped; /* pixels the step changed in the context's last denoise call; 0 when off */
+    double ms;       /* the step's device time in that call (HIP events); 0 when off */
+} lumo_firefly_info;
+/* cfg NULL: off, the state of a new context.  LUMO_ERR_INVALID for a NULL context, a field outside
+ * its range, a non-finite one or min_alike < rank; the setting is then as it was. */
+lumo_status lumo_denoise_set_firefly(void* ctx, const lumo_firefly_cfg* cfg);
+/* Of the context's last lumo_denoise / lumo_denoise_temporal call whose arguments were valid (zeros
+ * before the first, when the clamp was off, and when that call then failed). */
+lumo_status lumo_denoise_firefly_info(void* ctx, lumo_firefly_info* info);
 
 #ifdef __cplusplus
 }

@@ -960,6 +960,28 @@ class Device:
         """lumo_denoise_reset: drops the history; the next denoise_temporal call is a first frame."""
         check(lib().lumo_denoise_reset(self.ctx), "denoise_reset")
 
+    def set_firefly(self, cfg={}, **fields):
+        """lumo_denoise_set_firefly: the rank-order firefly clamp that denoise and denoise_temporal
+        of this context run between prepare and everything after it.
+        set_firefly(**fields) turns it on with lumo_firefly_cfg's defaults and `fields` (radius,
+        rank, min_alike, gain, normal_cos_min, depth_rel_max) over them, as does set_firefly(dict);
+        set_firefly(None) turns it off, the state of a new context."""
+        if cfg is None:
+            return check(lib().lumo_denoise_set_firefly(self.ctx, None), "set_firefly")
+        fields = {**cfg, **fields}
+        unknown = set(fields) - set(_ffi.FIREFLY_DEFAULTS)
+        if unknown:
+            raise TypeError(f"set_firefly: unknown field(s) {sorted(unknown)}")
+        c = _ffi.FireflyCfg(**{**_ffi.FIREFLY_DEFAULTS, **fields})
+        check(lib().lumo_denoise_set_firefly(self.ctx, C.byref(c)), "set_firefly")
+
+    def firefly_info(self):
+        """lumo_denoise_firefly_info: {"clamped": pixels the clamp changed in this context's last
+        denoise / denoise_temporal call, "ms": the step's device time}; zeros when it is off."""
+        info = _ffi.FireflyInfo()
+        check(lib().lumo_denoise_firefly_info(self.ctx, C.byref(info)), "firefly_info")
+        return {"clamped": info.clamped, "ms": info.ms}
+
     def trace(self, origins, dirs, lights=None):
         """lumo_trace: closest hit (Scene::hit, scene.rs:119-147) of each ray, or with `lights`
         the visibility of that light (Scene::hit_light, scene.rs:165-189).  Returns t, kind
@@ -1140,10 +1162,12 @@ class Renderer:
         dev.close()
         return film
 
-    def render_denoised(self, **cfg):
+    def render_denoised(self, firefly=None, **cfg):
         """(film, features, denoised): render() and render_features() of the frame with the renderer's
         seed (set .seed(), as render_features asks), then Device.denoise of the two with `cfg`
-        (lumo_denoise_cfg's fields) as a DenoisedFilm.  The filter works on linear radiance: a tone
+        (lumo_denoise_cfg's fields) as a DenoisedFilm.  firefly: None, or a dict of
+        Device.set_firefly's fields ({}: the defaults) for the clamp ahead of the filter.  The
+        filter works on linear radiance: a tone
         map set on the renderer is not applied to the render it filters.  Single-rank; with several
         GPUs render the shards, reduce the films and the feature films to one rank and call
         Device.denoise there."""
@@ -1157,24 +1181,26 @@ class Renderer:
         features = self.render_features()
         dev = Device(self._device)
         try:
+            dev.set_firefly(firefly)
             out = dev.denoise(film, features, **cfg)
         finally:
             dev.close()
         return film, features, DenoisedFilm(out, film.color_space)
 
-    def render_denoised_sequence(self, cameras, **cfg):
+    def render_denoised_sequence(self, cameras, firefly=None, **cfg):
         """Yields (film, features, denoised) per camera of `cameras` (each with the renderer's camera's
         resolution): render_denoised's frame with that camera, denoised by Device.denoise_temporal on
         one context whose history is reset at the start, so frame k accumulates frames 0 .. k - 1.
         Frame k is rendered with seed (seed + k) mod 2^64 of the renderer's .seed(), which must be
-        set.  `cfg`: the fields Device.denoise_temporal takes.  The renderer's own camera and seed
-        are as before afterwards."""
+        set.  `cfg`: the fields Device.denoise_temporal takes; firefly: as render_denoised's, set on
+        that context.  The renderer's own camera and seed are as before afterwards."""
         if self._seed is None:
             raise ValueError("Renderer.render_denoised_sequence: set .seed()")
         seed, camera, tone = self._seed, self.camera, self._tone_map
         dev = Device(self._device)
         try:
             dev.denoise_reset()
+            dev.set_firefly(firefly)
             for k, cam in enumerate(cameras):
                 self._seed, self.camera, self._tone_map = (seed + k) & 0xFFFFFFFFFFFFFFFF, cam, ToneMap.NO_MAP
                 film = self.render()

@@ -235,6 +235,19 @@ TEMPORAL_DEFAULTS = dict(alpha=0.2, normal_cos_min=0.9, depth_rel_max=0.1, max_h
                          stage_lds=1)
 
 
+class FireflyCfg(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("rank", C.c_int32), ("min_alike", C.c_int32), ("reserved", C.c_int32),
+                ("gain", C.c_double), ("normal_cos_min", C.c_double), ("depth_rel_max", C.c_double)]
+
+
+class FireflyInfo(C.Structure):
+    _fields_ = [("clamped", C.c_int64), ("ms", C.c_double)]
+
+
+# lumo_firefly_cfg's defaults, by field (the clamp itself is off until it is set)
+FIREFLY_DEFAULTS = dict(radius=2, rank=2, min_alike=4, gain=1.0, normal_cos_min=0.9, depth_rel_max=0.1)
+
+
 # lumo_feature_dump: (field, numpy dtype, values per sample), in the struct's order
 FEATURE_DUMP_FIELDS = [("kind", "i4", 1), ("object", "i4", 1), ("prim", "i4", 1), ("material", "i4", 1),
                        ("backface", "i4", 1), ("t", "f8", 1), ("p", "f8", 3), ("ng", "f8", 3), ("ns", "f8", 3),
@@ -278,6 +291,8 @@ DEVICE_API = [
     ("lumo_denoise_temporal", C.c_int32, [C.c_void_p, C.POINTER(DenoiseIn), C.POINTER(CameraDesc), C.POINTER(DenoiseCfg),
                                           C.POINTER(TemporalCfg), c_double_p, c_double_p, C.POINTER(TemporalInfo)]),
     ("lumo_denoise_reset", C.c_int32, [C.c_void_p]),
+    ("lumo_denoise_set_firefly", C.c_int32, [C.c_void_p, C.POINTER(FireflyCfg)]),
+    ("lumo_denoise_firefly_info", C.c_int32, [C.c_void_p, C.POINTER(FireflyInfo)]),
 ]
 HOST_API = [
     ("lumo_spectrum_from_rgb", Spectrum, [C.c_double, C.c_double, C.c_double]),

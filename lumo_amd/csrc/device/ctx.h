@@ -126,6 +126,10 @@ struct Ctx {
     int dn_hist_set = 0;
     int64_t dn_hist_w = 0, dn_hist_h = 0;  // 0: no history
     lumo_camera_desc dn_hist_cam{};
+    // the denoiser's firefly clamp (lumo_denoise_set_firefly): the setting, and what the last call did
+    bool dn_ff_on = false;
+    lumo_firefly_cfg dn_ff{};
+    lumo_firefly_info dn_ff_info{};
     lumo_stats stats{};
     lumo_schedule_info sched{};  // of the last render
     Timing tm;

@@ -1,14 +1,16 @@
 // lumo_denoise and lumo_denoise_temporal: the entry points of the denoiser (device/denoise.h,
 // DESIGN.md §4d; device/denoise_temporal.h, §4e).  A call uploads a frame's beauty film and feature
-// planes, runs prepare, (the reprojection of the context's history,) the variance estimate, the
-// a-trous iterations and finish on the context's main stream, and reads the result back.  Neither
-// needs a scene or touches the stats or the schedule record.
+// planes, runs prepare, (the firefly clamp when the context has it set: device/denoise_firefly.h,
+// §4f,) (the reprojection of the context's history,) the variance estimate, the a-trous iterations
+// and finish on the context's main stream, and reads the result back.  Neither needs a scene or
+// touches the stats or the schedule record.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "ctx.h"
 #include "denoise.h"
+#include "denoise_firefly.h"
 #include "denoise_temporal.h"
 
 using namespace lumo;
@@ -17,8 +19,17 @@ using namespace lumo::dev;
 namespace {
 
 // Device buffers of a call (Ctx::dn_work), grown on demand and kept for the next call.
-enum DnBuf { DN_IN_RGB, DN_IN_ALB, DN_IN_NRM, DN_IN_DEP, DN_IN_ADD, DN_PLANES, DN_HIT, DN_OUT, DN_BUF_COUNT };
+// DN_FF_CNT, the firefly clamp's counter, exists only on a context that has the clamp set.
+enum DnBuf { DN_IN_RGB, DN_IN_ALB, DN_IN_NRM, DN_IN_DEP, DN_IN_ADD, DN_PLANES, DN_HIT, DN_OUT, DN_FF_CNT, DN_BUF_COUNT };
 constexpr int DN_NPLANES = 3 + 1 + 1 + 3 + 1 + 2 * 3 + 2;  // the doubles of DnPlanes per pixel
+
+bool fcfg_valid(const lumo_firefly_cfg& f) {
+    for (double v : {f.gain, f.normal_cos_min, f.depth_rel_max})
+        if (!std::isfinite(v)) return false;
+    return f.radius >= 1 && f.radius <= DF_R && f.rank >= 1 && f.rank <= DF_TOP && f.min_alike >= f.rank &&
+           f.min_alike <= (2 * DF_R + 1) * (2 * DF_R + 1) - 1 && f.reserved == 0 && f.gain >= 1.0 && f.gain <= 1e6 &&
+           f.normal_cos_min >= -1.0 && f.normal_cos_min <= 1.0 && f.depth_rel_max >= 0.0 && f.depth_rel_max <= 1e6;
+}
 
 bool cfg_valid(const lumo_denoise_cfg& g) {
     for (double v : {g.sigma_l, g.sigma_z, g.albedo_floor, g.depth_floor, g.lum_floor})
@@ -63,7 +74,12 @@ struct DnCall {
     size_t bytes[DN_BUF_COUNT];
     unsigned pix_blocks;
     hipStream_t sm;
+    hipEvent_t ff_ev[2] = {};  // around the firefly clamp, when the context has it set
 
+    ~DnCall() {
+        for (hipEvent_t e : ff_ev)
+            if (e) (void)hipEventDestroy(e);
+    }
     double* buf(int k) const { return static_cast<double*>(c->dn_work[k].p); }
 
     lumo_status open(void* ctx, const lumo_denoise_in* in_, const lumo_denoise_cfg* cfg, const double* rgb_out) {
@@ -78,14 +94,17 @@ struct DnCall {
         dc = DnCfg{g.sigma_l, g.sigma_z, g.albedo_floor, g.depth_floor, g.lum_floor, g.normal_log2_power, g.demodulate};
         pix_blocks = (unsigned)((n + 255) / 256);
         sm = c->streams[0];
+        c->dn_ff_info = lumo_firefly_info{0, 0.0};  // until this call has run the step
         return LUMO_OK;
     }
     lumo_status alloc() {
         if (c->dn_work.size() < DN_BUF_COUNT) c->dn_work.resize(DN_BUF_COUNT);
         const size_t b[DN_BUF_COUNT] = {32 * n, 32 * n, 32 * n, 32 * n, in->add_rgb ? 24 * n : 0,
-                                        sizeof(double) * DN_NPLANES * n, sizeof(uint32_t) * n, 24 * n};
+                                        sizeof(double) * DN_NPLANES * n, sizeof(uint32_t) * n, 24 * n,
+                                        c->dn_ff_on ? sizeof(unsigned long long) : 0};
         for (int k = 0; k < DN_BUF_COUNT; ++k) {
             bytes[k] = b[k];
+            if (k == DN_FF_CNT && !b[k]) continue;
             const lumo_status st = dev_alloc(*c, c->dn_work[k], bytes[k]);
             if (st) return st;
         }
@@ -111,6 +130,31 @@ struct DnCall {
     void prepare() const {
         k_dn_prepare<<<pix_blocks, 256, 0, sm>>>(buf(DN_IN_RGB), buf(DN_IN_ALB), buf(DN_IN_NRM), buf(DN_IN_DEP),
                                                  in->add_rgb ? buf(DN_IN_ADD) : nullptr, P, dc, W, H);
+    }
+    // Step 1b, after prepare and before anything reads its e or l.  The factor plane is var[1], which
+    // nothing holds until the first a-trous iteration writes it.  Off: nothing is launched.
+    lumo_status firefly() {
+        if (!c->dn_ff_on) return LUMO_OK;
+        const lumo_firefly_cfg& f = c->dn_ff;
+        const DfCfg fc{f.gain, f.normal_cos_min, f.depth_rel_max, f.radius, f.rank, f.min_alike};
+        unsigned long long* cnt = static_cast<unsigned long long*>(c->dn_work[DN_FF_CNT].p);
+        for (hipEvent_t& e : ff_ev) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipEventRecord(ff_ev[0], sm));
+        HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), sm));
+        k_dn_firefly<<<march_grid(1), DN_BW, DnMarch<DF_R>::lds_bytes(1, DF_NV), sm>>>(P, fc, P.var[1], cnt, W, H);
+        k_dn_firefly_apply<<<pix_blocks, 256, 0, sm>>>(buf(DN_IN_RGB), in->add_rgb ? buf(DN_IN_ADD) : nullptr, P, P.var[1], n);
+        HIPCHK(hipEventRecord(ff_ev[1], sm));
+        return LUMO_OK;
+    }
+    // after the call's stream is idle: what the step did
+    lumo_status firefly_read() const {
+        if (!c->dn_ff_on) return LUMO_OK;
+        unsigned long long count = 0;
+        float ms = 0.0f;
+        HIPCHK(hipMemcpy(&count, c->dn_work[DN_FF_CNT].p, sizeof(count), hipMemcpyDeviceToHost));
+        HIPCHK(hipEventElapsedTime(&ms, ff_ev[0], ff_ev[1]));
+        c->dn_ff_info = lumo_firefly_info{(int64_t)count, (double)ms};
+        return LUMO_OK;
     }
     // the march kernels: x tiles of DN_BW centres; per residue class mod s, chunks of DN_ROWS rows
     dim3 march_grid(int s) const {
@@ -180,6 +224,7 @@ extern "C" lumo_status lumo_denoise(void* ctx, const lumo_denoise_in* in, const 
     if ((st = k.upload())) return st;
     clk.mark();
     k.prepare();
+    if ((st = k.firefly())) return st;
     clk.mark();
     k.variance();
     clk.mark();
@@ -193,7 +238,23 @@ extern "C" lumo_status lumo_denoise(void* ctx, const lumo_denoise_in* in, const 
     if ((st = k.read_back(set, rgb_out, variance_out))) return st;
     clk.mark();
     HIPCHK(hipStreamSynchronize(k.sm));
+    if ((st = k.firefly_read())) return st;
     if (k.g.stage_ms) clk.read(k.g.stage_ms);
+    return LUMO_OK;
+}
+
+extern "C" lumo_status lumo_denoise_set_firefly(void* ctx, const lumo_firefly_cfg* cfg) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || (cfg && !fcfg_valid(*cfg))) return LUMO_ERR_INVALID;
+    c->dn_ff_on = cfg != nullptr;
+    if (cfg) c->dn_ff = *cfg;
+    return LUMO_OK;
+}
+
+extern "C" lumo_status lumo_denoise_firefly_info(void* ctx, lumo_firefly_info* info) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !info) return LUMO_ERR_INVALID;
+    *info = c->dn_ff_info;
     return LUMO_OK;
 }
 
@@ -234,6 +295,7 @@ extern "C" lumo_status lumo_denoise_temporal(void* ctx, const lumo_denoise_in* i
     HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * DT_CNT_N, k.sm));
     clk.mark();
     k.prepare();
+    if ((st = k.firefly())) return st;
     clk.mark();
     const unsigned tiles = (unsigned)((k.W + DT_BX - 1) / DT_BX) * (unsigned)((k.H + DT_BY - 1) / DT_BY);
     k_dn_reproject<<<tiles, DT_THREADS, 0, k.sm>>>(k.P, prev, next, cam_of(*camera),
@@ -260,6 +322,7 @@ extern "C" lumo_status lumo_denoise_temporal(void* ctx, const lumo_denoise_in* i
     unsigned long long counts[DT_CNT_N] = {};
     HIPCHK(hipMemcpyAsync(counts, cnt, sizeof(counts), hipMemcpyDeviceToHost, k.sm));
     HIPCHK(hipStreamSynchronize(k.sm));
+    if ((st = k.firefly_read())) return st;
     if (info) {
         info->with_history = (int64_t)counts[DT_CNT_WITH];
         info->without_history = (int64_t)counts[DT_CNT_WITHOUT];

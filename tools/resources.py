@@ -1,7 +1,8 @@
 """Kernel resources of the device code as the compiler reports them (-Rpass-analysis=
 kernel-resource-usage): VGPRs, SGPRs, spilled SGPRs / VGPRs, scratch bytes per lane, waves per SIMD.
-Compiles the instantiation units for the given stack classes, kernels.hip, denoise.hip and the host-only units
-ctx.hip / upload.hip (device only), then prints a markdown table.  Usage: python tools/resources.py [STK ...] > profiles/<round>/resources.md"""
+Compiles the instantiation units for the given stack classes, kernels.hip, denoise.hip (the kernels of denoise.h,
+denoise_firefly.h and denoise_temporal.h, with the Makefile's flags for that unit) and the host-only units
+ctx.hip / upload.hip (device only), then prints a markdown table with each kernel's static LDS.  Usage: python tools/resources.py [STK ...] > profiles/<round>/resources.md"""
 import os
 import re
 import subprocess
@@ -38,17 +39,18 @@ def main():
     stks = sys.argv[1:] or ["0", "4"]
     units = [(f"lumo_amd/csrc/device/inst_{k}.hip", [f"-DLUMO_STK={s}"]) for s in stks for k in ("pt", "bd")]
     units.append(("lumo_amd/csrc/device/kernels.hip", []))
-    units.append(("lumo_amd/csrc/device/denoise.hip", []))
+    units.append(("lumo_amd/csrc/device/denoise.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]))
     # host-only units: they must add no row
     units += [("lumo_amd/csrc/device/ctx.hip", []), ("lumo_amd/csrc/device/upload.hip", [])]
-    print("| kernel | VGPRs | SGPRs | SGPR spills | VGPR spills | scratch B/lane | waves/SIMD |")
-    print("|---|---|---|---|---|---|---|")
+    print("| kernel | VGPRs | SGPRs | SGPR spills | VGPR spills | scratch B/lane | waves/SIMD | static LDS B/block |")
+    print("|---|---|---|---|---|---|---|---|")
     for src, defs in units:
         for r in remarks(src, defs):
             if "ScratchSize [bytes/lane]" not in r:
                 continue
             print(f"| `{demangle(r['name'])}` | {r.get('VGPRs')} | {r.get('TotalSGPRs')} | {r.get('SGPRs Spill')} | "
-                  f"{r.get('VGPRs Spill')} | {r.get('ScratchSize [bytes/lane]')} | {r.get('Occupancy [waves/SIMD]')} |")
+                  f"{r.get('VGPRs Spill')} | {r.get('ScratchSize [bytes/lane]')} | {r.get('Occupancy [waves/SIMD]')} | "
+                  f"{r.get('LDS Size [bytes/block]')} |")
 
 
 if __name__ == "__main__":

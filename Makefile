@@ -21,12 +21,16 @@ HOST_OBJ := $(patsubst lumo_amd/csrc/host/%.cpp,build/host/%.o,$(HOST_SRC))
 # their own translation units, so they compile in parallel: inst_pt.hip / inst_bd.hip built with
 # -DLUMO_STK=<class>.
 STK_CLASSES := 0 4 8 16 24 32 48 64
-MAIN_OBJ := $(BUILD)/device/kernels.o $(BUILD)/device/ctx.o $(BUILD)/device/upload.o $(BUILD)/device/denoise.o
+MAIN_OBJ := $(BUILD)/device/kernels.o $(BUILD)/device/ctx.o $(BUILD)/device/upload.o $(BUILD)/device/denoise.o \
+            $(BUILD)/device/wbvh_dev.o
 # denoise.hip is all f64: compiled without the packed f32 instructions
 FLAGS_denoise := -Xclang -target-feature -Xclang -packed-fp32-ops
+# wbvh_dev.hip is the device builder of the wide BVH (the kernels of wbvh_dev.h): f64 and integers
+FLAGS_wbvh_dev := -Xclang -target-feature -Xclang -packed-fp32-ops
 DEV_OBJ  := $(MAIN_OBJ) $(foreach k,$(STK_CLASSES),$(BUILD)/device/inst_pt_$(k).o $(BUILD)/device/inst_bd_$(k).o)
 CTX_H    := lumo_amd/csrc/device/ctx.h lumo_amd/csrc/host/wbvh.h
-DEV_H    := $(filter-out $(CTX_H),$(wildcard lumo_amd/csrc/device/*.h))
+WBDEV_H  := lumo_amd/csrc/device/wbvh_dev.h
+DEV_H    := $(filter-out $(CTX_H) $(WBDEV_H),$(wildcard lumo_amd/csrc/device/*.h))
 COMMON_H := $(wildcard lumo_amd/csrc/common/*.h) include/lumo_amd.h include/lumo_host.h
 
 LIB      ?= lumo_amd/liblumo_amd.so
@@ -42,6 +46,7 @@ build/host/%.o: lumo_amd/csrc/host/%.cpp $(COMMON_H) $(wildcard lumo_amd/csrc/ho
 $(MAIN_OBJ): $(BUILD)/device/%.o: lumo_amd/csrc/device/%.hip $(COMMON_H) $(DEV_H) $(CTX_H)
 	@mkdir -p $(BUILD)/device
 	$(HIPCC) $(HIPFLAGS) $(DEVFLAGS) $(FLAGS_$*) -c $< -o $@
+$(BUILD)/device/wbvh_dev.o: $(WBDEV_H)
 
 $(BUILD)/device/inst_pt_%.o: lumo_amd/csrc/device/inst_pt.hip $(COMMON_H) $(DEV_H)
 	@mkdir -p $(BUILD)/device

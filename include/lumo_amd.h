@@ -760,6 +760,73 @@ lumo_status lumo_denoise_set_firefly(void* ctx, const lumo_firefly_cfg* cfg);
  * before the first, when the clamp was off, and when that call then failed). */
 lumo_status lumo_denoise_firefly_info(void* ctx, lumo_firefly_info* info);
 
+/* ---------------------------------------------------------------------------------
+ * Device builder of the wide BVH (LUMO_OPT_ACCEL = 1).  By default the upload builds the 4-wide BVH
+ * on the host (binned SAH, seconds for a large scene).  lumo_scene_set_wide_build lets a context
+ * build it on the GPU instead, as an LBVH, in milliseconds: for scenes whose geometry changes from
+ * frame to frame.  Same node format, same arrays, same walks; the tree differs, so the traversal
+ * counters do, and a ray that ties between two triangles of one tree may keep the other one.
+ * Per-context state read by the next lumo_scene_upload, as the firefly clamp's; an addition within
+ * ABI 10, the capability check is the presence of lumo_scene_set_wide_build (dlsym).
+ *
+ * The construction, step by step (f64 throughout; deterministic: no float atomics, positions from
+ * scans, the one atomic counter per node only decides which thread carries on):
+ *   0 host      per tree (world objects, world lights, one BLAS per distinct (tri_base, count)): its
+ *               runs of triangles and its object leaves (a sphere, an instance) with their world
+ *               boxes by the host builder's rules.  The refusal of light kd trees deeper than 16
+ *               levels stays here.
+ *   1 boxes     per primitive the exact f64 min / max of its vertices; centroid 0.5 lo + 0.5 hi;
+ *               per tree the bounds of the centroids.
+ *   2 keys      63-bit Morton key, 21 bits per axis (x most significant): cell =
+ *               (c - lo) / (hi - lo) 2^21 truncated, at most 2^21 - 1; a zero extent or a NaN: cell 0.
+ *   3 sort      stable LSD radix sort of (tree, key), 8-bit digits, starting from primitive order:
+ *               equal keys stay in primitive order.
+ *   4 tree      Karras's binary radix tree per tree; delta(i, j) = clz(key_i ^ key_j), and
+ *               64 + clz(i ^ j) (32-bit positions) when the keys are equal.
+ *   5 fit       bottom-up: box = union of the children's, primitive count, "holds an object leaf".
+ *               A subtree of at most leaf_max primitives, none an object leaf, is a leaf when its
+ *               parent is none; an object leaf is a leaf of its own (count 0).  Leaf records are
+ *               the triangles in sorted order.
+ *   6 collapse  level by level from every tree's root (objects, lights, BLASes): a node's children
+ *               are its two binary children, then, while fewer than 4, the largest-half-area child
+ *               that is no leaf replaced in place by its two (the first such on ties).  Node
+ *               indices are level-major, children in item order.  Boxes narrow to f32 outward:
+ *               cast, compare back in f64, one ulp by nextafter.  Unused slots: lo 1, hi -1, ref NONE.
+ *   7 derived   levels; max |coordinate|; walk-stack need n - 1 + the largest child need, an
+ *               instance leaf 1 + the deepest BLAS need; refused above stack_limit or at 2^27 leaf
+ *               records.  sah_cost (both builders): over the trees whose root is a node, the sum
+ *               over nodes and children of child half-area / half-area of the union of the root's
+ *               child boxes, times the triangle count of a leaf (1 for a node or an object leaf).
+ * Asked for the device builder and refused: the host builder; that refused too: lumo's structures.
+ * ------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t builder;     /* 0 host SAH (default), 1 device LBVH; read at the next upload with accel = 1 */
+    int32_t leaf_max;    /* 1 .. 8 (default 8): triangles per leaf of the device builder */
+    int32_t stack_limit; /* 1 .. 64 (default 64): the device build is refused above this walk-stack need */
+    int32_t reserved;    /* 0 */
+} lumo_wide_build_cfg;
+/* cfg NULL: the defaults.  LUMO_ERR_INVALID for a NULL context or a field outside its range; the
+ * setting is then as it was. */
+lumo_status lumo_scene_set_wide_build(void* ctx, const lumo_wide_build_cfg* cfg);
+
+typedef struct {
+    int32_t builder_asked, builder_used;   /* used: -1 when the scene is walked on lumo's structures */
+    int32_t trees;     /* trees with a primitive (world objects, world lights, BLASes) */
+    int32_t levels;    /* node levels (lumo_scene_info's wide_depth + 1; 0: no node) */
+    int32_t nodes, tris, stack, reserved;
+    double build_ms;   /* device builder: HIP events around steps 1-7; host builder: wall clock of its build */
+    double sah_cost;
+} lumo_wide_build_info;
+/* Of the last upload (zeros with builder_used -1 when accel = 0).  LUMO_ERR_NO_SCENE before one. */
+lumo_status lumo_scene_wide_build_info(void* ctx, lumo_wide_build_info* info);
+
+/* Test hook: the wide BVH of the uploaded scene as it lies on the device, whichever builder made it.
+ * Two calls: with only info (8 values: accel on, nodes, leaf records, stack, depth, objects root,
+ * lights root, 0) for the sizes, then with the arrays (nodes x 128 B, records x 10 doubles, one
+ * BLAS root per object and per light).  LUMO_ERR_NO_SCENE before an upload. */
+lumo_status lumo_debug_wide_export(void* ctx, int64_t* info, void* nodes, double* tv, int32_t* obj_blas,
+                                   int32_t* light_blas);
+
 #ifdef __cplusplus
 }
 #endif

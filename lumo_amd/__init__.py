@@ -780,7 +780,9 @@ class DenoisedFilm:
 class Device:
     """One lumo_amd context bound to one GPU (lumo_create)."""
 
-    def __init__(self, device=0, **options):
+    def __init__(self, device=0, wide_build=None, leaf_max=None, stack_limit=None, **options):
+        """options: execution options (LUMO_OPT_*).  wide_build ("host" | "device"), leaf_max and
+        stack_limit: set_wide_build's, the builder of the wide BVH an upload with accel=1 uses."""
         L = lib()
         ctx = C.c_void_p()
         st = L.lumo_create(device, C.byref(ctx))
@@ -790,6 +792,46 @@ class Device:
         self.scene = None
         for k, v in options.items():  # execution options (LUMO_OPT_*), e.g. Device(0, split_pipe=1)
             self.set_option(k, v)
+        if (wide_build, leaf_max, stack_limit) != (None, None, None):
+            self.set_wide_build(wide_build or "host", leaf_max=leaf_max, stack_limit=stack_limit)
+
+    def set_wide_build(self, builder="host", leaf_max=None, stack_limit=None):
+        """lumo_scene_set_wide_build: which builder the next upload with accel=1 makes the wide BVH
+        with: "host", the binned SAH build, or "device", the LBVH built on the GPU in
+        milliseconds (for geometry that changes between frames; it walks somewhat slower).  leaf_max
+        (1..8) and stack_limit (1..64) are the device builder's; None: the defaults."""
+        if builder not in _ffi.WIDE_BUILDERS:
+            raise ValueError(f"set_wide_build: builder {builder!r} is not one of {sorted(_ffi.WIDE_BUILDERS)}")
+        f = dict(_ffi.WIDE_BUILD_DEFAULTS, builder=_ffi.WIDE_BUILDERS[builder])
+        f.update({k: int(v) for k, v in (("leaf_max", leaf_max), ("stack_limit", stack_limit)) if v is not None})
+        check(lib().lumo_scene_set_wide_build(self.ctx, C.byref(_ffi.WideBuildCfg(**f))), "set_wide_build")
+        return self
+
+    def wide_build_info(self):
+        """lumo_scene_wide_build_info of the last upload, as a dict: builder_asked, builder_used (-1: lumo's
+        structures), trees, levels, nodes, tris, stack, build_ms, sah_cost."""
+        info = _ffi.WideBuildInfo()
+        check(lib().lumo_scene_wide_build_info(self.ctx, C.byref(info)), "wide_build_info")
+        return {k: getattr(info, k) for k, _ in _ffi.WideBuildInfo._fields_ if k != "reserved"}
+
+    def wide_export(self):
+        """lumo_debug_wide_export: the uploaded scene's wide BVH as it lies on the device: dict with ok, nodes
+        (structured array: lo, hi (3 x 4 f32), ref (4), n), tv (records x 10 doubles), the records' tri / obj
+        ids, stack, depth, obj_root, light_root and the BLAS root of every object and light."""
+        info = (C.c_int64 * 8)()
+        check(lib().lumo_debug_wide_export(self.ctx, info, None, None, None, None), "wide_export")
+        nn, nt = int(info[1]), int(info[2])
+        no, nl = self._scene_desc.num_objects, self._scene_desc.num_lights
+        nodes = np.zeros(max(nn, 1), dtype=np.dtype(_ffi.WNODE))
+        tv = np.zeros((max(nt, 1), 10))
+        ob, lb = np.zeros(max(no, 1), dtype=np.int32), np.zeros(max(nl, 1), dtype=np.int32)
+        check(lib().lumo_debug_wide_export(self.ctx, info, nodes.ctypes.data_as(C.c_void_p), _dptr(tv),
+                                           ob.ctypes.data_as(_ffi.c_int32_p), lb.ctypes.data_as(_ffi.c_int32_p)),
+              "wide_export")
+        ids = tv[:, 9].copy().view(np.int32).reshape(-1, 2)
+        return dict(ok=bool(info[0]), nodes=nodes[:nn], tv=tv[:nt], tri=ids[:nt, 0], obj=ids[:nt, 1],
+                    stack=int(info[3]), depth=int(info[4]), obj_root=int(info[5]), light_root=int(info[6]),
+                    obj_blas=ob[:no], light_blas=lb[:nl])
 
     def upload(self, scene, camera=None):
         L = lib()

@@ -248,6 +248,23 @@ class FireflyInfo(C.Structure):
 FIREFLY_DEFAULTS = dict(radius=2, rank=2, min_alike=4, gain=1.0, normal_cos_min=0.9, depth_rel_max=0.1)
 
 
+class WideBuildCfg(C.Structure):
+    _fields_ = [("builder", C.c_int32), ("leaf_max", C.c_int32), ("stack_limit", C.c_int32), ("reserved", C.c_int32)]
+
+
+class WideBuildInfo(C.Structure):
+    _fields_ = [("builder_asked", C.c_int32), ("builder_used", C.c_int32), ("trees", C.c_int32), ("levels", C.c_int32),
+                ("nodes", C.c_int32), ("tris", C.c_int32), ("stack", C.c_int32), ("reserved", C.c_int32),
+                ("build_ms", C.c_double), ("sah_cost", C.c_double)]
+
+
+# lumo_wide_build_cfg's defaults, by field, and the builders by name
+WIDE_BUILD_DEFAULTS = dict(builder=0, leaf_max=8, stack_limit=64)
+WIDE_BUILDERS = {"host": 0, "device": 1}
+# wide BVH node (csrc/common/wbvh.h Node, 128 B) as lumo_debug_wide_export returns it
+WNODE = [("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("ref", "<i4", 4), ("n", "<i4"), ("pad", "<i4", 3)]
+
+
 # lumo_feature_dump: (field, numpy dtype, values per sample), in the struct's order
 FEATURE_DUMP_FIELDS = [("kind", "i4", 1), ("object", "i4", 1), ("prim", "i4", 1), ("material", "i4", 1),
                        ("backface", "i4", 1), ("t", "f8", 1), ("p", "f8", 3), ("ng", "f8", 3), ("ns", "f8", 3),
@@ -293,6 +310,9 @@ DEVICE_API = [
     ("lumo_denoise_reset", C.c_int32, [C.c_void_p]),
     ("lumo_denoise_set_firefly", C.c_int32, [C.c_void_p, C.POINTER(FireflyCfg)]),
     ("lumo_denoise_firefly_info", C.c_int32, [C.c_void_p, C.POINTER(FireflyInfo)]),
+    ("lumo_scene_set_wide_build", C.c_int32, [C.c_void_p, C.POINTER(WideBuildCfg)]),
+    ("lumo_scene_wide_build_info", C.c_int32, [C.c_void_p, C.POINTER(WideBuildInfo)]),
+    ("lumo_debug_wide_export", C.c_int32, [C.c_void_p, c_int64_p, C.c_void_p, c_double_p, c_int32_p, c_int32_p]),
 ]
 HOST_API = [
     ("lumo_spectrum_from_rgb", Spectrum, [C.c_double, C.c_double, C.c_double]),

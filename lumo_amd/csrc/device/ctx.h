@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../../include/lumo_amd.h"
+#include "../common/wbvh_dev_prep.h"
 #include "state.h"
 
 namespace lumo {
@@ -159,10 +160,28 @@ struct Ctx {
     hipEvent_t bd_ev[4] = {};
     V3 sort_lo{0.0, 0.0, 0.0}, sort_scale{0.0, 0.0, 0.0};  // ray sorting: the scene's world box -> 512 cells per axis
     int w_nodes = 0, w_tris = 0, w_stack = 0, w_depth = 0;     // the uploaded wide BVH (lumo_scene_info)
+    // which builder the next upload with accel = 1 uses (lumo_scene_set_wide_build), and what the last did
+    lumo_wide_build_cfg wb_cfg{0, 8, 64, 0};
+    lumo_wide_build_info wb_info{};
 };
 
 lumo_status dev_alloc(const Ctx& c, DevBuf& b, size_t bytes);
 void free_scene(Ctx& c);
+
+// The device builder of the wide BVH (wbvh_dev.hip).  ok = false: refused (the walk-stack need above
+// the context's stack_limit, or a size the node format cannot hold); max_stack says what it needed.
+// nodes and tv are the finished arrays on the device; the caller owns them (wide_dev_free, or the
+// scene's buffer list).
+struct WideDev {
+    bool ok = false;
+    DevBuf nodes, tv;
+    int n_nodes = 0, n_tv = 0, max_stack = 0, levels = 0;
+    float max_abs = 0.0f;
+    double sah = 0.0, ms = 0.0;
+    std::vector<int32_t> root_ref;  // per tree of the DevPrep
+};
+lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangles, WideDev& out);
+void wide_dev_free(WideDev& wd);
 
 template <typename T>
 lumo_status upload(Ctx& c, const T* host, size_t count, const T** dptr) {

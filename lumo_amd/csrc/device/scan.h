@@ -35,8 +35,10 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* l
     return incl - v;
 }
 
+// The two kernels and their launcher are static: each unit that includes this header (kernels.hip,
+// wbvh_dev.hip) holds copies of its own, and the library links without a clash.
 // Block sums: block b totals in[b * SCAN_TILE .. (b + 1) * SCAN_TILE).
-__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_sums(const uint32_t* in, uint32_t n, uint32_t* sums) {
+static __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_sums(const uint32_t* in, uint32_t n, uint32_t* sums) {
     __shared__ uint32_t lds[SCAN_BLOCK];
     const size_t base = (size_t)blockIdx.x * SCAN_TILE;
     uint32_t s = 0;
@@ -52,8 +54,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_sums(const uint32_t* in, ui
 
 // Scan: block b adds the totals of blocks 0 .. b - 1, then scans its tile (thread t owns the
 // SCAN_ITEMS consecutive counts t * SCAN_ITEMS ..).  `out` may alias nothing in `in`.
-__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_apply(const uint32_t* in, uint32_t* out, uint32_t n,
-                                                           const uint32_t* sums) {
+static __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_apply(const uint32_t* in, uint32_t* out, uint32_t n,
+                                                                  const uint32_t* sums) {
     __shared__ uint32_t lds[SCAN_BLOCK];
     uint32_t pre = 0;
     for (uint32_t b = threadIdx.x; b < blockIdx.x; b += SCAN_BLOCK) pre += sums[b];
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_apply(const uint32_t* in, u
 inline int scan_blocks(uint32_t n) { return (int)((n + SCAN_TILE - 1) / SCAN_TILE); }
 
 // out[i] = in[0] + ... + in[i - 1]; `sums` holds scan_blocks(n) values.
-inline hipError_t exclusive_scan(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* sums, hipStream_t sm) {
+static inline hipError_t exclusive_scan(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* sums, hipStream_t sm) {
     if (n == 0) return hipSuccess;
     const int nb = scan_blocks(n);
     k_scan_sums<<<nb, SCAN_BLOCK, 0, sm>>>(in, n, sums);

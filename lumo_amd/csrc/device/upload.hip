@@ -1,9 +1,11 @@
 // Scene upload, camera and scene information (host code only: no kernel is defined or launched
 // here): the device layouts of lumo's structures (breadth-first BVHs, kd treelets, the LDS-staged
-// sets), the optional wide accel, the scene's stack and feature classes.
+// sets), the optional wide accel (built here on the host, or by wbvh_dev.hip on the device), the
+// scene's stack and feature classes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -302,22 +304,96 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
     s.off_top_wnodes = 0;
     s.off_wnodes = s.off_wtv = s.off_woblas = s.off_wlblas = 0;
     c->w_nodes = c->w_tris = c->w_stack = c->w_depth = 0;
+    // The device builder (lumo_scene_set_wide_build, wbvh_dev.hip) leaves the nodes and the records
+    // on the device: acc then holds the scalars and the BLAS roots, and of nodes / tv only what
+    // fetch_wide has read back for the staged sets below.  n_wnodes / n_wtv are the whole arrays.
+    bool dev_built = false;
+    size_t n_wnodes = 0, n_wtv = 0;
+    c->wb_info = lumo_wide_build_info{};
+    c->wb_info.builder_asked = c->wb_cfg.builder;
+    c->wb_info.builder_used = -1;
+    auto fetch_wide = [&](size_t nodes, bool records) {
+        if (dev_built && acc.nodes.size() < nodes) {
+            acc.nodes.resize(nodes);
+            if (hipMemcpy(acc.nodes.data(), s.wnodes, sizeof(wbvh::Node) * nodes, hipMemcpyDeviceToHost) != hipSuccess)
+                chk(LUMO_ERR_HIP);
+        }
+        if (dev_built && records && acc.tv.size() < n_wtv * wbvh::TV) {
+            acc.tv.resize(n_wtv * wbvh::TV);
+            if (hipMemcpy(acc.tv.data(), s.wtv, sizeof(double) * acc.tv.size(), hipMemcpyDeviceToHost) != hipSuccess)
+                chk(LUMO_ERR_HIP);
+        }
+    };
+    if (c->o.accel && !st && c->wb_cfg.builder == 1) {
+        const wbvh::DevPrep prep = wbvh::prepare_device_build(*d);  // refuses what build_accel refuses of the lights
+        WideDev wd;
+        if (prep.ok) chk(wide_build_device(*c, prep, d->num_triangles, wd));
+        if (!st && wd.ok) {
+            dev_built = true;
+            acc.ok = true;
+            acc.obj_root = wd.root_ref[0];
+            acc.light_root = wd.root_ref[1];
+            acc.obj_blas.assign(d->num_objects > 0 ? d->num_objects : 0, wbvh::NONE);
+            acc.light_blas.assign(d->num_lights > 0 ? d->num_lights : 0, wbvh::NONE);
+            for (const auto& x : prep.inst_tree)
+                (x.first >> 30 ? acc.light_blas : acc.obj_blas)[x.first & ((1 << 30) - 1)] = wd.root_ref[x.second];
+            acc.max_stack = wd.max_stack;
+            acc.depth = wd.levels > 0 ? wd.levels - 1 : 0;
+            acc.max_abs = wd.max_abs;
+            n_wnodes = (size_t)wd.n_nodes;
+            n_wtv = (size_t)wd.n_tv;
+            c->scene_bufs.push_back(wd.nodes);
+            c->scene_bufs.push_back(wd.tv);
+            s.wnodes = static_cast<const wbvh::Node*>(wd.nodes.p);
+            s.wtv = static_cast<const double*>(wd.tv.p);
+            c->wb_info.build_ms = wd.ms;
+            c->wb_info.sah_cost = wd.sah;
+            c->wb_info.levels = wd.levels;
+            c->wb_info.trees = (int)std::count_if(wd.root_ref.begin(), wd.root_ref.end(),
+                                                  [](int32_t r) { return r != wbvh::NONE; });
+        } else {
+            wide_dev_free(wd);
+            if (!st && wd.max_stack > c->wb_cfg.stack_limit)
+                fprintf(stderr, "lumo_amd: the device builder of the wide accel refused this scene (a walk stack of "
+                        "%d above %d); building on the host\n", wd.max_stack, c->wb_cfg.stack_limit);
+            else if (!st)
+                fprintf(stderr, "lumo_amd: the device builder of the wide accel refused this scene (a light kd tree "
+                        "deeper than %d, 2^27 leaf records, 2^30 primitives or more than 65535 trees); building on "
+                        "the host\n", WL_STK);
+        }
+    }
     if (c->o.accel && !st) {
-        acc = wbvh::build_accel(*d);  // refuses light kd trees deeper than WL_STK
+        if (!dev_built) {
+            const auto t0 = std::chrono::steady_clock::now();
+            acc = wbvh::build_accel(*d);  // refuses light kd trees deeper than WL_STK
+            c->wb_info.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            n_wnodes = acc.nodes.size();
+            n_wtv = acc.tv.size() / wbvh::TV;
+        }
         if (acc.ok) {
             s.accel = 1;
             s.w_oroot = acc.obj_root;
             s.w_lroot = acc.light_root;
             s.w_maxabs = (double)acc.max_abs;
-            chk(upload(*c, acc.nodes.data(), acc.nodes.size(), &s.wnodes));
-            chk(upload(*c, acc.tv.data(), acc.tv.size(), &s.wtv));
+            if (!dev_built) {
+                chk(upload(*c, acc.nodes.data(), acc.nodes.size(), &s.wnodes));
+                chk(upload(*c, acc.tv.data(), acc.tv.size(), &s.wtv));
+                c->wb_info.sah_cost = wbvh::accel_sah_cost(acc);
+                c->wb_info.trees = wbvh::accel_tree_count(acc);
+                c->wb_info.levels = acc.nodes.empty() ? 0 : acc.depth + 1;
+            }
             chk(upload(*c, acc.obj_blas.data(), acc.obj_blas.size(), &s.w_oblas));
             chk(upload(*c, acc.light_blas.data(), acc.light_blas.size(), &s.w_lblas));
-            c->w_nodes = (int)acc.nodes.size();
-            c->w_tris = (int)(acc.tv.size() / wbvh::TV);
+            c->w_nodes = (int)n_wnodes;
+            c->w_tris = (int)n_wtv;
             c->w_stack = acc.max_stack;
             c->w_depth = acc.depth;
+            c->wb_info.builder_used = dev_built ? 1 : 0;
+            c->wb_info.nodes = c->w_nodes;
+            c->wb_info.tris = c->w_tris;
+            c->wb_info.stack = c->w_stack;
         } else {
+            c->wb_info.build_ms = 0.0;
             fprintf(stderr, "lumo_amd: the wide accel refused this scene (a light kd tree deeper than %d or a "
                     "walk stack of %d); walking lumo's structures\n", WL_STK, acc.max_stack);
         }
@@ -351,14 +427,18 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
         s.off_xforms = put(d->transforms, sizeof(lumo_transform) * d->num_transforms);
         s.off_tobjs = put(tobjs.data(), sizeof(DObj) * tobjs.size());
         s.off_tlights = put(tlights.data(), sizeof(DObj) * tlights.size());
-        if (s.accel) {
+        // a device-built tree is read back only when the set can fit (each put pads to 16 B)
+        const bool wide_fits = !dev_built || hot.size() + sizeof(wbvh::Node) * n_wnodes + sizeof(double) * wbvh::TV * n_wtv +
+                                                 sizeof(int32_t) * (acc.obj_blas.size() + acc.light_blas.size()) <= 48 * 1024;
+        if (s.accel && wide_fits) {
+            fetch_wide(n_wnodes, true);
             s.off_wnodes = put(acc.nodes.data(), sizeof(wbvh::Node) * acc.nodes.size());
             s.off_wtv = put(acc.tv.data(), sizeof(double) * acc.tv.size());
             s.off_woblas = put(acc.obj_blas.data(), sizeof(int32_t) * acc.obj_blas.size());
             s.off_wlblas = put(acc.light_blas.data(), sizeof(int32_t) * acc.light_blas.size());
         }
         s.hot_bytes = 0;
-        if (hot.size() <= 48 * 1024) {
+        if (hot.size() <= 48 * 1024 && wide_fits) {
             const char* dp = nullptr;
             chk(upload(*c, hot.data(), hot.size(), &dp));
             if (st) {
@@ -394,7 +474,8 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
             s.off_top_oitems = 0;
             s.off_top_tobjs = put(tobjs.data(), sizeof(DObj) * tobjs.size());
             const size_t left = budget - top.size();
-            const size_t nw = std::min(acc.nodes.size(), left / sizeof(wbvh::Node));
+            const size_t nw = std::min(n_wnodes, left / sizeof(wbvh::Node));
+            fetch_wide(nw, false);
             s.off_top_wnodes = put(acc.nodes.data(), sizeof(wbvh::Node) * nw);
             s.top_wnodes = (int32_t)nw;
             s.top_onodes = s.top_lnodes = 0;
@@ -529,6 +610,10 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
     }
     full = full || c->o.full_kernels != 0;  // A/B switch
     s.full = textured ? 2 : (full ? 1 : 0);
+    if (st) {  // a read-back of the device-built tree failed
+        free_scene(*c);
+        return st;
+    }
     c->has_scene = true;
     return LUMO_OK;
 }

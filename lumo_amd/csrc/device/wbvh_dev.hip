@@ -1,0 +1,305 @@
+// Device builder of the wide BVH: the launches of the kernels of wbvh_dev.h, and
+// the entry points lumo_scene_set_wide_build, lumo_scene_wide_build_info and lumo_debug_wide_export.
+// lumo_scene_upload (upload.hip) calls wide_build_device when the context asks for this builder.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "ctx.h"
+#include "wbvh_dev.h"
+
+using namespace lumo;
+using namespace lumo::dev;
+
+namespace {
+
+// workspace of one build: freed when the build returns
+struct Bufs {
+    std::vector<DevBuf> v;
+    ~Bufs() {
+        for (DevBuf& b : v)
+            if (b.p) (void)hipFree(b.p);
+    }
+    template <typename T>
+    lumo_status get(const Ctx& c, T** p, size_t count) {
+        v.emplace_back();
+        const lumo_status st = dev_alloc(c, v.back(), sizeof(T) * std::max<size_t>(count, 1));
+        *p = static_cast<T*>(v.back().p);
+        return st;
+    }
+    template <typename T>
+    lumo_status put(const Ctx& c, const T** p, const std::vector<T>& host) {
+        T* q = nullptr;
+        const lumo_status st = get(c, &q, host.size());
+        if (st) return st;
+        if (!host.empty()) HIPCHK(hipMemcpy(q, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice));
+        *p = q;
+        return LUMO_OK;
+    }
+};
+
+inline int blocks(size_t n) { return (int)((n + WB_BLOCK - 1) / WB_BLOCK); }
+
+#define WB_TRY(x)                      \
+    do {                               \
+        const lumo_status s__ = (x);   \
+        if (s__) return s__;           \
+    } while (0)
+
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    uint32_t* pinned = nullptr;
+    ~Events() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        if (pinned) (void)hipHostFree(pinned);
+    }
+};
+
+}  // namespace
+
+namespace lumo {
+namespace dev {
+
+void wide_dev_free(WideDev& wd) {
+    for (DevBuf* b : {&wd.nodes, &wd.tv})
+        if (b->p) {
+            (void)hipFree(b->p);
+            *b = DevBuf{};
+        }
+}
+
+lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangles, WideDev& out) {
+    out = WideDev{};
+    const int T = (int)prep.tree_base.size() - 1;
+    if (T < 2 || T > 65535 || !prep.ok) return LUMO_OK;  // 65535: the tree is a grid dimension (k_wb_cb_partial)
+    const size_t N = (size_t)prep.tree_base[T];
+    for (const wbvh::DevSeg& s : prep.segs)
+        if (s.tri_base >= 0 && (s.count <= 0 || (int64_t)s.tri_base + s.count > num_triangles)) return LUMO_OK;
+    out.root_ref.assign(T, wbvh::NONE);
+    if (N == 0) {  // no primitive anywhere: every root NONE
+        WB_TRY(dev_alloc(c, out.nodes, 0));
+        WB_TRY(dev_alloc(c, out.tv, 0));
+        out.ok = true;
+        return LUMO_OK;
+    }
+    hipStream_t sm = c.streams[0];
+    Bufs ws;
+    Events ev;
+    HIPCHK(hipEventCreate(&ev.a));
+    HIPCHK(hipEventCreate(&ev.b));
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ev.pinned), sizeof(uint32_t) * 2));
+    WbWork w{};
+    w.n_prims = (int32_t)N;
+    w.n_trees = T;
+    w.n_segs = (int32_t)prep.segs.size();
+    w.leaf_max = c.wb_cfg.leaf_max;
+    w.vertices = c.sc.vertices;
+    w.tris = c.sc.tris;
+    WB_TRY(ws.put(c, &w.segs, prep.segs));
+    WB_TRY(ws.put(c, &w.tree_base, prep.tree_base));
+    WB_TRY(ws.put(c, &w.obj_box, prep.obj_box));
+    uint64_t* key[2];
+    uint32_t* idx[2];
+    uint32_t *flag, *hist, *offs, *sums;
+    const int rx_blocks = (int)((N + RX_TILE - 1) / RX_TILE);
+    const size_t n_hist = (size_t)RX_BINS * rx_blocks;
+    WB_TRY(ws.get(c, &w.pbox, N));
+    WB_TRY(ws.get(c, &w.ptri, N));
+    WB_TRY(ws.get(c, &w.pobj, N));
+    WB_TRY(ws.get(c, &w.cbound, (size_t)T));
+    WB_TRY(ws.get(c, &w.cpart, (size_t)T * WB_RED_GRID));
+    for (int k = 0; k < 2; ++k) {
+        WB_TRY(ws.get(c, &key[k], N));
+        WB_TRY(ws.get(c, &idx[k], N));
+    }
+    WB_TRY(ws.get(c, &w.child, 2 * N));
+    WB_TRY(ws.get(c, &w.iparent, N));
+    WB_TRY(ws.get(c, &w.lparent, N));
+    WB_TRY(ws.get(c, &w.ifirst, N));
+    WB_TRY(ws.get(c, &w.ibox, N));
+    WB_TRY(ws.get(c, &w.icount, N));
+    WB_TRY(ws.get(c, &w.iflag, N));
+    WB_TRY(ws.get(c, &w.rec_pos, N));
+    WB_TRY(ws.get(c, &w.root_ref, (size_t)T));
+    WB_TRY(ws.get(c, &w.scal, 1));
+    WB_TRY(ws.get(c, &flag, N));
+    WB_TRY(ws.get(c, &hist, n_hist));
+    WB_TRY(ws.get(c, &offs, n_hist));
+    WB_TRY(ws.get(c, &sums, (size_t)scan_blocks((uint32_t)std::max({n_hist, N, (size_t)T}))));
+    WB_TRY(dev_alloc(c, out.tv, sizeof(double) * wbvh::TV * (size_t)prep.n_tris));
+    w.tv = static_cast<double*>(out.tv.p);
+    // scan[n - 1] + in[n - 1] of an exclusive scan: its total (one small read-back and a wait)
+    auto total = [&](const uint32_t* in, const uint32_t* scan, size_t n, uint32_t* sum) -> lumo_status {
+        HIPCHK(hipMemcpyAsync(ev.pinned, in + n - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, sm));
+        HIPCHK(hipMemcpyAsync(ev.pinned + 1, scan + n - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, sm));
+        HIPCHK(hipStreamSynchronize(sm));
+        *sum = ev.pinned[0] + ev.pinned[1];
+        return LUMO_OK;
+    };
+    const int nb = blocks(N), tb = blocks((size_t)T);
+
+    HIPCHK(hipEventRecord(ev.a, sm));
+    // 1. boxes, centroid bounds  2. keys
+    w.key = key[0];
+    w.idx = idx[0];
+    k_wb_fill<<<1, WB_BLOCK, 0, sm>>>(reinterpret_cast<uint32_t*>(w.scal), 0u, (uint32_t)(sizeof(WbScal) / 4));
+    k_wb_fill<<<nb, WB_BLOCK, 0, sm>>>(w.iflag, 0u, (uint32_t)N);
+    k_wb_prims<<<nb, WB_BLOCK, 0, sm>>>(w);
+    k_wb_cb_partial<<<dim3(WB_RED_GRID, T), WB_BLOCK, 0, sm>>>(w);
+    k_wb_cb_final<<<T, WB_RED_GRID, 0, sm>>>(w);
+    k_wb_morton<<<nb, WB_BLOCK, 0, sm>>>(w);
+    // 3. sort by (tree, key): the 8 key digits, then the tree's
+    const int passes = 8 + (T <= 256 ? 1 : (T <= 65536 ? 2 : 3));
+    int cur = 0;
+    for (int p = 0; p < passes; ++p) {
+        k_rx_hist<<<rx_blocks, WB_BLOCK, 0, sm>>>(key[cur], idx[cur], (uint32_t)N, p, w.tree_base, T, hist);
+        HIPCHK(exclusive_scan(hist, offs, (uint32_t)n_hist, sums, sm));
+        k_rx_scatter<<<rx_blocks, WB_BLOCK, 0, sm>>>(key[cur], idx[cur], (uint32_t)N, p, w.tree_base, T, offs, key[cur ^ 1],
+                                                     idx[cur ^ 1]);
+        cur ^= 1;
+    }
+    w.key = key[cur];
+    w.idx = idx[cur];
+    // 4. radix tree  5. boxes bottom-up; the records in sorted order
+    k_wb_radix<<<nb, WB_BLOCK, 0, sm>>>(w);
+    k_wb_fit<<<nb, WB_BLOCK, 0, sm>>>(w);
+    k_wb_recflag<<<nb, WB_BLOCK, 0, sm>>>(w, flag);
+    HIPCHK(exclusive_scan(flag, w.rec_pos, (uint32_t)N, sums, sm));
+    k_wb_records<<<nb, WB_BLOCK, 0, sm>>>(w);
+    // 6. collapse.  The wide nodes are at most the binary nodes that are no leaves.
+    uint32_t cap = 0;
+    k_wb_openflag<<<nb, WB_BLOCK, 0, sm>>>(w, flag);
+    HIPCHK(exclusive_scan(flag, w.iflag, (uint32_t)N, sums, sm));  // iflag: free after k_wb_fit
+    HIPCHK(hipGetLastError());
+    WB_TRY(total(flag, w.iflag, N, &cap));
+    const size_t lists = std::max<size_t>({(size_t)cap, (size_t)T, 1});
+    uint32_t *cnt, *pos, *n_kids;
+    int32_t *kids, *items[2];
+    double* rarea;
+    float* pmax;
+    double* psum;
+    WB_TRY(ws.get(c, &cnt, lists));
+    WB_TRY(ws.get(c, &pos, lists));
+    WB_TRY(ws.get(c, &n_kids, lists));
+    WB_TRY(ws.get(c, &kids, 4 * lists));
+    WB_TRY(ws.get(c, &items[0], lists));
+    WB_TRY(ws.get(c, &items[1], lists));
+    WB_TRY(ws.get(c, &w.wtree, lists));
+    WB_TRY(ws.get(c, &w.need, lists));
+    WB_TRY(ws.get(c, &rarea, (size_t)T));
+    WB_TRY(ws.get(c, &pmax, (size_t)WB_STAT_GRID));
+    WB_TRY(ws.get(c, &psum, (size_t)WB_STAT_GRID));
+    WB_TRY(dev_alloc(c, out.nodes, sizeof(wbvh::Node) * (size_t)cap));
+    w.nodes = static_cast<wbvh::Node*>(out.nodes.p);
+    uint32_t n_items = 0;
+    k_wb_roots_count<<<tb, WB_BLOCK, 0, sm>>>(w, cnt);
+    HIPCHK(exclusive_scan(cnt, pos, (uint32_t)T, sums, sm));
+    WB_TRY(total(cnt, pos, (size_t)T, &n_items));
+    k_wb_roots_emit<<<tb, WB_BLOCK, 0, sm>>>(w, pos, items[0]);
+    std::vector<int32_t> level_start;
+    uint32_t base = 0;
+    cur = 0;
+    while (n_items > 0) {
+        level_start.push_back((int32_t)base);
+        if ((size_t)base + n_items > cap) return LUMO_ERR_INVALID;  // cannot happen: cap counts every candidate
+        uint32_t next = 0;
+        k_wb_open<<<blocks(n_items), WB_BLOCK, 0, sm>>>(w, items[cur], n_items, kids, n_kids, cnt);
+        HIPCHK(exclusive_scan(cnt, pos, n_items, sums, sm));
+        WB_TRY(total(cnt, pos, n_items, &next));
+        if ((size_t)base + n_items + next > cap) return LUMO_ERR_INVALID;
+        k_wb_emit<<<blocks(n_items), WB_BLOCK, 0, sm>>>(w, n_items, kids, n_kids, pos, (int32_t)base,
+                                                        (int32_t)(base + n_items), items[cur ^ 1]);
+        base += n_items;
+        n_items = next;
+        cur ^= 1;
+    }
+    level_start.push_back((int32_t)base);
+    const int levels = (int)level_start.size() - 1;
+    // 7. stack need (deepest level first, BLASes before the world trees), max_abs, SAH cost
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int l = levels - 1; l >= 0; --l)
+            k_wb_need<<<blocks((size_t)(level_start[l + 1] - level_start[l])), WB_BLOCK, 0, sm>>>(w, level_start[l],
+                                                                                                 level_start[l + 1], pass);
+        k_wb_rootneed<<<1, WB_BLOCK, 0, sm>>>(w, pass);
+    }
+    if (base > 0) {
+        const int grid = std::min(blocks(base), WB_STAT_GRID);
+        k_wb_rootarea<<<tb, WB_BLOCK, 0, sm>>>(w, rarea);
+        k_wb_stats_partial<<<grid, WB_BLOCK, 0, sm>>>(w, (int32_t)base, rarea, pmax, psum);
+        k_wb_stats_final<<<1, WB_BLOCK, 0, sm>>>(w, grid, pmax, psum);
+    }
+    HIPCHK(hipEventRecord(ev.b, sm));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(sm));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    WbScal sc{};
+    HIPCHK(hipMemcpy(&sc, w.scal, sizeof(sc), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out.root_ref.data(), w.root_ref, sizeof(int32_t) * (size_t)T, hipMemcpyDeviceToHost));
+    out.n_nodes = (int)base;
+    out.n_tv = (int)prep.n_tris;
+    out.levels = levels;
+    out.max_stack = sc.max_stack;
+    out.max_abs = sc.max_abs;
+    out.sah = sc.sah;
+    out.ms = (double)ms;
+    out.ok = sc.max_stack <= c.wb_cfg.stack_limit && base < (uint32_t)INT32_MAX / 2;
+    return LUMO_OK;
+}
+
+}  // namespace dev
+}  // namespace lumo
+
+extern "C" {
+
+lumo_status lumo_scene_set_wide_build(void* ctx, const lumo_wide_build_cfg* cfg) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c) return LUMO_ERR_INVALID;
+    const lumo_wide_build_cfg v = cfg ? *cfg : lumo_wide_build_cfg{0, 8, 64, 0};
+    if (v.builder < 0 || v.builder > 1 || v.leaf_max < 1 || v.leaf_max > 8 || v.stack_limit < 1 ||
+        v.stack_limit > wbvh::STACK || v.reserved != 0)
+        return LUMO_ERR_INVALID;
+    c->wb_cfg = v;
+    return LUMO_OK;
+}
+
+lumo_status lumo_scene_wide_build_info(void* ctx, lumo_wide_build_info* info) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !info) return LUMO_ERR_INVALID;
+    if (!c->has_scene) return LUMO_ERR_NO_SCENE;
+    *info = c->wb_info;
+    return LUMO_OK;
+}
+
+lumo_status lumo_debug_wide_export(void* ctx, int64_t* info, void* nodes, double* tv, int32_t* obj_blas,
+                                   int32_t* light_blas) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !info) return LUMO_ERR_INVALID;
+    if (!c->has_scene) return LUMO_ERR_NO_SCENE;
+    HIPCHK(hipSetDevice(c->device));
+    const DScene& s = c->sc;
+    const bool on = s.accel != 0;
+    info[0] = on;
+    info[1] = on ? c->w_nodes : 0;
+    info[2] = on ? c->w_tris : 0;
+    info[3] = on ? c->w_stack : 0;
+    info[4] = on ? c->w_depth : 0;
+    info[5] = on ? s.w_oroot : wbvh::NONE;
+    info[6] = on ? s.w_lroot : wbvh::NONE;
+    info[7] = 0;
+    if (!on) return LUMO_OK;
+    if (nodes && c->w_nodes)
+        HIPCHK(hipMemcpy(nodes, s.wnodes, sizeof(wbvh::Node) * (size_t)c->w_nodes, hipMemcpyDeviceToHost));
+    if (tv && c->w_tris)
+        HIPCHK(hipMemcpy(tv, s.wtv, sizeof(double) * wbvh::TV * (size_t)c->w_tris, hipMemcpyDeviceToHost));
+    if (obj_blas && s.n_objs > 0)
+        HIPCHK(hipMemcpy(obj_blas, s.w_oblas, sizeof(int32_t) * (size_t)s.n_objs, hipMemcpyDeviceToHost));
+    if (light_blas && s.n_lights > 0)
+        HIPCHK(hipMemcpy(light_blas, s.w_lblas, sizeof(int32_t) * (size_t)s.n_lights, hipMemcpyDeviceToHost));
+    return LUMO_OK;
+}
+
+}  // extern "C"

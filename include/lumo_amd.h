@@ -820,6 +820,50 @@ typedef struct {
 /* Of the last upload (zeros with builder_used -1 when accel = 0).  LUMO_ERR_NO_SCENE before one. */
 lumo_status lumo_scene_wide_build_info(void* ctx, lumo_wide_build_info* info);
 
+/* ---------------------------------------------------------------------------------
+ * Clustered device builder.  The LBVH above splits where the Morton keys say; its SAH cost is 1.3 to
+ * 2.2 times the host tree's.  lumo_scene_set_wide_cluster has the device builder make its binary tree
+ * bottom-up by surface area instead: parallel locally-ordered clustering (PLOC, Meister & Bittner
+ * 2018).  A second per-context setting, read by the next upload with accel = 1 when the device
+ * builder is used and inert otherwise; an addition within ABI 10, found by dlsym like the above.
+ * Steps 0 to 3 and 6 to 7 above stay; in place of 4 and 5 (f64, no atomic, positions from scans):
+ *   4' clusters  one cluster per sorted primitive: its ref, tree and box, a compact array in Morton
+ *               order.  A tree's clusters are contiguous and stay so.
+ *   5' iterate   until every tree is one cluster.  (a) Each cluster i finds its nearest neighbour
+ *               among the clusters j of its tree with 0 < |i - j| <= radius: the smallest half-area
+ *               of the union box (min / max, then dx dy + dy dz + dz dx; a negative or NaN extent: 0;
+ *               a NaN area: +inf), the smaller j on ties.  (b) Every pair that chose each other
+ *               becomes one internal node: children (i, j) for i < j, box the union, primitive
+ *               count, "holds an object leaf"; it takes i's place and j leaves, the others keep
+ *               their order.  A tree of `live` clusters gives the merges of an iteration the slots
+ *               base + live - 2 downward in cluster order, so its root is slot base.  Every tree of
+ *               two or more clusters merges at least one pair per iteration.  After max_iter
+ *               iterations (a) is replaced by pairing clusters 2k and 2k + 1 of each tree, which
+ *               halves every tree: nested boxes can merge one pair per iteration.
+ *   5'' relabel a leaf's position within its tree becomes the number of primitives to its left in
+ *               the binary tree, so every subtree is a range of positions again; leaf records are
+ *               the triangles in that order, and a leaf is chosen as in 5.
+ * ------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t radius;    /* 0 (default): the LBVH, exactly as above.  1 .. 64: PLOC with this search radius */
+    int32_t max_iter;  /* 0: the built-in cap.  1 .. 4096: nearest-neighbour iterations before
+                          the builder switches to pairing adjacent clusters */
+    int32_t reserved[2];  /* 0 */
+} lumo_wide_cluster_cfg;
+/* cfg NULL: the defaults.  LUMO_ERR_INVALID for a NULL context, a field outside its range or a
+ * non-zero reserved; the setting is then as it was. */
+lumo_status lumo_scene_set_wide_cluster(void* ctx, const lumo_wide_cluster_cfg* cfg);
+
+typedef struct {
+    int32_t radius_used;        /* 0 whenever the LBVH, the host tree or lumo's structures were used */
+    int32_t iterations;         /* nearest-neighbour iterations */
+    int32_t paired_iterations;  /* iterations that paired adjacent clusters */
+    int32_t reserved;
+    double cluster_ms;          /* HIP events around steps 4' to 5''; lumo_wide_build_info.build_ms holds them too */
+} lumo_wide_cluster_info;
+/* Of the last upload.  LUMO_ERR_NO_SCENE before one. */
+lumo_status lumo_scene_wide_cluster_info(void* ctx, lumo_wide_cluster_info* info);
+
 /* Test hook: the wide BVH of the uploaded scene as it lies on the device, whichever builder made it.
  * Two calls: with only info (8 values: accel on, nodes, leaf records, stack, depth, objects root,
  * lights root, 0) for the sizes, then with the arrays (nodes x 128 B, records x 10 doubles, one

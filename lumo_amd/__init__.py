@@ -780,9 +780,12 @@ class DenoisedFilm:
 class Device:
     """One lumo_amd context bound to one GPU (lumo_create)."""
 
-    def __init__(self, device=0, wide_build=None, leaf_max=None, stack_limit=None, **options):
+    def __init__(self, device=0, wide_build=None, leaf_max=None, stack_limit=None, wide_cluster=None,
+                 cluster_iters=None, **options):
         """options: execution options (LUMO_OPT_*).  wide_build ("host" | "device"), leaf_max and
-        stack_limit: set_wide_build's, the builder of the wide BVH an upload with accel=1 uses."""
+        stack_limit: set_wide_build's, the builder of the wide BVH an upload with accel=1 uses.
+        wide_cluster (a search radius; True: set_wide_cluster's default) and cluster_iters:
+        set_wide_cluster's, the clustered device builder; None: the LBVH."""
         L = lib()
         ctx = C.c_void_p()
         st = L.lumo_create(device, C.byref(ctx))
@@ -794,6 +797,27 @@ class Device:
             self.set_option(k, v)
         if (wide_build, leaf_max, stack_limit) != (None, None, None):
             self.set_wide_build(wide_build or "host", leaf_max=leaf_max, stack_limit=stack_limit)
+        if wide_cluster is True:
+            self.set_wide_cluster(max_iter=cluster_iters)
+        elif (wide_cluster, cluster_iters) != (None, None):
+            self.set_wide_cluster(wide_cluster or 0, max_iter=cluster_iters)
+
+    def set_wide_cluster(self, radius=_ffi.WIDE_CLUSTER_RADIUS, max_iter=None):
+        """lumo_scene_set_wide_cluster: how the device builder makes its binary tree at the next upload
+        (DESIGN.md §4g).  radius 1..64: PLOC, clusters merged bottom-up by the surface area of the
+        union within this many positions of the Morton order (a better tree than the LBVH for a
+        longer build); 0: the LBVH.  max_iter (1..4096; None: the built-in cap): nearest-neighbour
+        iterations before adjacent clusters are paired.  Inert while the host builder is used."""
+        cfg = _ffi.WideClusterCfg(radius=int(radius), max_iter=0 if max_iter is None else int(max_iter))
+        check(lib().lumo_scene_set_wide_cluster(self.ctx, C.byref(cfg)), "set_wide_cluster")
+        return self
+
+    def wide_cluster_info(self):
+        """lumo_scene_wide_cluster_info of the last upload, as a dict: radius_used (0: no clustered build),
+        iterations, paired_iterations, cluster_ms."""
+        info = _ffi.WideClusterInfo()
+        check(lib().lumo_scene_wide_cluster_info(self.ctx, C.byref(info)), "wide_cluster_info")
+        return {k: getattr(info, k) for k, _ in _ffi.WideClusterInfo._fields_ if k != "reserved"}
 
     def set_wide_build(self, builder="host", leaf_max=None, stack_limit=None):
         """lumo_scene_set_wide_build: which builder the next upload with accel=1 makes the wide BVH

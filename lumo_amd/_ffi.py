@@ -261,6 +261,20 @@ class WideBuildInfo(C.Structure):
 # lumo_wide_build_cfg's defaults, by field, and the builders by name
 WIDE_BUILD_DEFAULTS = dict(builder=0, leaf_max=8, stack_limit=64)
 WIDE_BUILDERS = {"host": 0, "device": 1}
+
+
+class WideClusterCfg(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("max_iter", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class WideClusterInfo(C.Structure):
+    _fields_ = [("radius_used", C.c_int32), ("iterations", C.c_int32), ("paired_iterations", C.c_int32),
+                ("reserved", C.c_int32), ("cluster_ms", C.c_double)]
+
+
+# Device.set_wide_cluster's default search radius: the best C2 / C3 geometric-mean short frame of
+# DESIGN.md §4g's table (lumo_wide_cluster_cfg's own default is 0: the LBVH)
+WIDE_CLUSTER_RADIUS = 32
 # wide BVH node (csrc/common/wbvh.h Node, 128 B) as lumo_debug_wide_export returns it
 WNODE = [("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("ref", "<i4", 4), ("n", "<i4"), ("pad", "<i4", 3)]
 
@@ -312,6 +326,8 @@ DEVICE_API = [
     ("lumo_denoise_firefly_info", C.c_int32, [C.c_void_p, C.POINTER(FireflyInfo)]),
     ("lumo_scene_set_wide_build", C.c_int32, [C.c_void_p, C.POINTER(WideBuildCfg)]),
     ("lumo_scene_wide_build_info", C.c_int32, [C.c_void_p, C.POINTER(WideBuildInfo)]),
+    ("lumo_scene_set_wide_cluster", C.c_int32, [C.c_void_p, C.POINTER(WideClusterCfg)]),
+    ("lumo_scene_wide_cluster_info", C.c_int32, [C.c_void_p, C.POINTER(WideClusterInfo)]),
     ("lumo_debug_wide_export", C.c_int32, [C.c_void_p, c_int64_p, C.c_void_p, c_double_p, c_int32_p, c_int32_p]),
 ]
 HOST_API = [

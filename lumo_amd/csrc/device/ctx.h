@@ -163,6 +163,9 @@ struct Ctx {
     // which builder the next upload with accel = 1 uses (lumo_scene_set_wide_build), and what the last did
     lumo_wide_build_cfg wb_cfg{0, 8, 64, 0};
     lumo_wide_build_info wb_info{};
+    // how the device builder makes its binary tree (lumo_scene_set_wide_cluster), and what the last upload did
+    lumo_wide_cluster_cfg wc_cfg{};
+    lumo_wide_cluster_info wc_info{};
 };
 
 lumo_status dev_alloc(const Ctx& c, DevBuf& b, size_t bytes);
@@ -179,6 +182,7 @@ struct WideDev {
     float max_abs = 0.0f;
     double sah = 0.0, ms = 0.0;
     std::vector<int32_t> root_ref;  // per tree of the DevPrep
+    lumo_wide_cluster_info cluster{};  // zeros: the LBVH
 };
 lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangles, WideDev& out);
 void wide_dev_free(WideDev& wd);

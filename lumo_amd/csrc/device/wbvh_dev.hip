@@ -1,5 +1,6 @@
-// Device builder of the wide BVH: the launches of the kernels of wbvh_dev.h, and
-// the entry points lumo_scene_set_wide_build, lumo_scene_wide_build_info and lumo_debug_wide_export.
+// Device builder of the wide BVH: the launches of the kernels of wbvh_dev.h and
+// wbvh_ploc.h, and the entry points lumo_scene_set_wide_build, lumo_scene_wide_build_info,
+// lumo_scene_set_wide_cluster, lumo_scene_wide_cluster_info and lumo_debug_wide_export.
 // lumo_scene_upload (upload.hip) calls wide_build_device when the context asks for this builder.
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,7 @@
 
 #include "ctx.h"
 #include "wbvh_dev.h"
+#include "wbvh_ploc.h"
 
 using namespace lumo;
 using namespace lumo::dev;
@@ -40,6 +42,10 @@ struct Bufs {
     }
 };
 
+// lumo_wide_cluster_cfg.max_iter = 0: nearest-neighbour iterations before adjacent clusters are paired;
+// twice the largest count measured, 78
+constexpr int PL_ITER_CAP = 156;
+
 inline int blocks(size_t n) { return (int)((n + WB_BLOCK - 1) / WB_BLOCK); }
 
 #define WB_TRY(x)                      \
@@ -49,11 +55,11 @@ inline int blocks(size_t n) { return (int)((n + WB_BLOCK - 1) / WB_BLOCK); }
     } while (0)
 
 struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
+    hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr;  // the build; its clustering
     uint32_t* pinned = nullptr;
     ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
+        for (hipEvent_t e : {a, b, c, d})
+            if (e) (void)hipEventDestroy(e);
         if (pinned) (void)hipHostFree(pinned);
     }
 };
@@ -90,6 +96,8 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
     Events ev;
     HIPCHK(hipEventCreate(&ev.a));
     HIPCHK(hipEventCreate(&ev.b));
+    HIPCHK(hipEventCreate(&ev.c));
+    HIPCHK(hipEventCreate(&ev.d));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ev.pinned), sizeof(uint32_t) * 2));
     WbWork w{};
     w.n_prims = (int32_t)N;
@@ -129,6 +137,23 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
     WB_TRY(ws.get(c, &hist, n_hist));
     WB_TRY(ws.get(c, &offs, n_hist));
     WB_TRY(ws.get(c, &sums, (size_t)scan_blocks((uint32_t)std::max({n_hist, N, (size_t)T}))));
+    // the clustered build (wbvh_ploc.h): the live clusters twice (120 B per primitive); its flags and
+    // their scan take the key buffers, which nobody reads after the sort, the relabelled idx the spare one
+    PlWork pl{};
+    uint32_t* pl_sums = nullptr;
+    pl.radius = c.wc_cfg.radius;
+    if (pl.radius > 0) {
+        for (int k = 0; k < 2; ++k) {
+            WB_TRY(ws.get(c, &pl.cref[k], N));
+            WB_TRY(ws.get(c, &pl.ctree[k], N));
+            WB_TRY(ws.get(c, &pl.cbox[k], N));
+            WB_TRY(ws.get(c, &pl.cstart[k], (size_t)T));
+        }
+        WB_TRY(ws.get(c, &pl.tlive, (size_t)T));
+        WB_TRY(ws.get(c, &pl.nn, N));
+        WB_TRY(ws.get(c, &pl.lpar, N));
+        WB_TRY(ws.get(c, &pl_sums, (size_t)scan_blocks((uint32_t)(2 * N))));
+    }
     WB_TRY(dev_alloc(c, out.tv, sizeof(double) * wbvh::TV * (size_t)prep.n_tris));
     w.tv = static_cast<double*>(out.tv.p);
     // scan[n - 1] + in[n - 1] of an exclusive scan: its total (one small read-back and a wait)
@@ -163,9 +188,44 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
     }
     w.key = key[cur];
     w.idx = idx[cur];
-    // 4. radix tree  5. boxes bottom-up; the records in sorted order
-    k_wb_radix<<<nb, WB_BLOCK, 0, sm>>>(w);
-    k_wb_fit<<<nb, WB_BLOCK, 0, sm>>>(w);
+    if (pl.radius > 0) {
+        // 4'. clusters  5'. merge mutual nearest neighbours until every tree is one cluster  5''. relabel
+        pl.flag = reinterpret_cast<uint32_t*>(key[0]);
+        pl.scan = reinterpret_cast<uint32_t*>(key[1]);
+        pl.idx_out = idx[cur ^ 1];
+        const int max_iter = c.wc_cfg.max_iter > 0 ? c.wc_cfg.max_iter : PL_ITER_CAP;
+        size_t roots = 0;  // clusters left when every tree is done
+        for (int t = 0; t < T; ++t) roots += prep.tree_base[t + 1] > prep.tree_base[t];
+        HIPCHK(hipEventRecord(ev.c, sm));
+        k_pl_init<<<nb, WB_BLOCK, 0, sm>>>(w, pl);
+        int pc = 0;
+        for (size_t n = N; n > roots;) {
+            const bool nearest = out.cluster.iterations < max_iter;
+            if (nearest)
+                k_pl_nearest<<<blocks(n), WB_BLOCK, 0, sm>>>(pl, pc, (int)n);
+            else
+                k_pl_pair<<<blocks(n), WB_BLOCK, 0, sm>>>(pl, pc, (int)n);
+            k_pl_flag<<<blocks(n), WB_BLOCK, 0, sm>>>(pl, pc, (int)n);
+            HIPCHK(exclusive_scan(pl.flag, pl.scan, (uint32_t)(2 * n), pl_sums, sm));
+            k_pl_merge<<<blocks(n), WB_BLOCK, 0, sm>>>(w, pl, pc, (int)n);
+            HIPCHK(hipMemcpyAsync(ev.pinned, pl.scan + n, sizeof(uint32_t), hipMemcpyDeviceToHost, sm));  // the merges
+            HIPCHK(hipStreamSynchronize(sm));
+            const uint32_t merged = ev.pinned[0];
+            if (merged > n - roots || (!nearest && merged == 0)) return LUMO_ERR_INVALID;  // cannot happen
+            (nearest ? out.cluster.iterations : out.cluster.paired_iterations)++;
+            n -= merged;
+            pc ^= 1;
+        }
+        k_pl_order<<<nb, WB_BLOCK, 0, sm>>>(w, pl);
+        HIPCHK(hipEventRecord(ev.d, sm));
+        w.idx = pl.idx_out;
+        out.cluster.radius_used = pl.radius;
+    } else {
+        // 4. radix tree  5. boxes bottom-up
+        k_wb_radix<<<nb, WB_BLOCK, 0, sm>>>(w);
+        k_wb_fit<<<nb, WB_BLOCK, 0, sm>>>(w);
+    }
+    // the records in sorted order
     k_wb_recflag<<<nb, WB_BLOCK, 0, sm>>>(w, flag);
     HIPCHK(exclusive_scan(flag, w.rec_pos, (uint32_t)N, sums, sm));
     k_wb_records<<<nb, WB_BLOCK, 0, sm>>>(w);
@@ -236,6 +296,11 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
     HIPCHK(hipStreamSynchronize(sm));
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (pl.radius > 0) {
+        float cms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&cms, ev.c, ev.d));
+        out.cluster.cluster_ms = (double)cms;
+    }
     WbScal sc{};
     HIPCHK(hipMemcpy(&sc, w.scal, sizeof(sc), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out.root_ref.data(), w.root_ref, sizeof(int32_t) * (size_t)T, hipMemcpyDeviceToHost));
@@ -271,6 +336,25 @@ lumo_status lumo_scene_wide_build_info(void* ctx, lumo_wide_build_info* info) {
     if (!c || !info) return LUMO_ERR_INVALID;
     if (!c->has_scene) return LUMO_ERR_NO_SCENE;
     *info = c->wb_info;
+    return LUMO_OK;
+}
+
+lumo_status lumo_scene_set_wide_cluster(void* ctx, const lumo_wide_cluster_cfg* cfg) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c) return LUMO_ERR_INVALID;
+    const lumo_wide_cluster_cfg v = cfg ? *cfg : lumo_wide_cluster_cfg{};
+    if (v.radius < 0 || v.radius > PL_RADIUS_MAX || v.max_iter < 0 || v.max_iter > 4096 || v.reserved[0] != 0 ||
+        v.reserved[1] != 0)
+        return LUMO_ERR_INVALID;
+    c->wc_cfg = v;
+    return LUMO_OK;
+}
+
+lumo_status lumo_scene_wide_cluster_info(void* ctx, lumo_wide_cluster_info* info) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !info) return LUMO_ERR_INVALID;
+    if (!c->has_scene) return LUMO_ERR_NO_SCENE;
+    *info = c->wc_info;
     return LUMO_OK;
 }
 

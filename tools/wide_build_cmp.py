@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """The two builders of the wide BVH side by side, on bench.py's stand-in scenes, one MI355X.
 
-Per config and builder ("host": binned SAH on the CPU, "device": the LBVH of device/wbvh_dev.h, per leaf_max):
-the build time of three uploads (lumo_wide_build_info.build_ms: host wall clock, device HIP events) and their
-median, the SAH cost, nodes, levels, stack need, and the wall clock of a short frame (tools/ab2.sh's: C2 at
-4 spp, C3 and C4 at 8 spp; one warm-up frame, then `--frames` timed ones; one context at a time).
+Per config and builder ("host": binned SAH on the CPU, "device": the LBVH of device/wbvh_dev.h or, with
+`--cluster RADIUS`, the clustered build of device/wbvh_ploc.h; per leaf_max and radius): the build time of three
+uploads (lumo_wide_build_info.build_ms: host wall clock, device HIP events) and their median, the clustering's
+share of it and its iterations, the SAH cost, nodes, levels, stack need, and the wall clock of a short frame
+(tools/ab2.sh's: C2 at 4 spp, C3 and C4 at 8 spp; one warm-up frame, then `--frames` timed ones; one context at
+a time).
 
-    python tools/wide_build_cmp.py [--configs c2 c3 c4] [--leaf-max 8 4] [--frames 3]  ->  one JSON line per case"""
+    python tools/wide_build_cmp.py [--configs c2 c3 c4] [--leaf-max 8 4] [--cluster 0 8 16 32] [--frames 3]
+        ->  one JSON line per case"""
 import argparse
 import json
 import os
@@ -23,6 +26,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--configs", nargs="*", default=["c2", "c3", "c4"], choices=sorted(SPP))
     ap.add_argument("--leaf-max", nargs="*", type=int, default=[8, 4])
+    ap.add_argument("--cluster", nargs="*", type=int, default=[0], metavar="RADIUS",
+                    help="device cases per search radius of the clustered builder (0: the LBVH)")
+    ap.add_argument("--cluster-iters", type=int, default=None, help="lumo_wide_cluster_cfg.max_iter (default: the built-in cap)")
+    ap.add_argument("--no-host", action="store_true", help="leave the host builder's case out")
     ap.add_argument("--frames", type=int, default=3)
     ap.add_argument("--max-paths", type=int, default=1 << 23, help="paths in flight per wavefront (bench.py's default)")
     ap.add_argument("--res", type=int, default=None, help="square frames of this size instead of the configs' own")
@@ -36,16 +43,20 @@ def main():
 
         def render(dev):  # BDPT's light-tracing splats are collected and dropped
             dev.render_tasks(tasks, max_paths=a.max_paths, integrator=integrator, splats_out=[] if integrator else None)
-        cases = [("host", 8)] + [("device", m) for m in a.leaf_max]
-        for builder, leaf_max in cases:  # one context at a time: a C3 context's work buffers take much of the HBM
-            print(f"{cfg}: {builder} builder, leaf_max {leaf_max}", file=sys.stderr, flush=True)
-            dev = L.Device(0, accel=1, wide_build=builder, leaf_max=leaf_max)
+        cases = ([] if a.no_host else [("host", 8, 0)]) + [("device", m, r) for r in a.cluster for m in a.leaf_max]
+        for builder, leaf_max, radius in cases:  # one context at a time: a C3 context's work buffers take much of the HBM
+            print(f"{cfg}: {builder} builder, leaf_max {leaf_max}, cluster radius {radius}", file=sys.stderr, flush=True)
+            dev = L.Device(0, accel=1, wide_build=builder, leaf_max=leaf_max, wide_cluster=radius,
+                           cluster_iters=a.cluster_iters)
             try:
-                builds = []
+                builds, clusters = [], []
                 for _ in range(3):
                     dev.upload(scene, cam)
                     builds.append(dev.wide_build_info())
-                info = builds[-1]
+                    clusters.append(dev.wide_cluster_info())
+                info, how = builds[-1], clusters[-1]
+                if how["radius_used"] != radius:
+                    raise SystemExit(f"{cfg}: asked for cluster radius {radius}, got {how['radius_used']}")
                 if info["builder_used"] != L._ffi.WIDE_BUILDERS[builder]:
                     raise SystemExit(f"{cfg}: asked for the {builder} builder, got {info['builder_used']}")
                 render(dev)  # warm-up
@@ -59,6 +70,8 @@ def main():
             print(json.dumps({"config": cfg, "builder": builder, "leaf_max": leaf_max, "frame": [W, H, spp],
                               "build_ms": [round(b["build_ms"], 3) for b in builds],
                               "build_ms_median": round(statistics.median(b["build_ms"] for b in builds), 3),
+                              "cluster": radius, "cluster_ms": [round(c["cluster_ms"], 3) for c in clusters],
+                              "iterations": [how["iterations"], how["paired_iterations"]],
                               "sah_cost": round(info["sah_cost"], 3),
                               **{k: info[k] for k in ("trees", "levels", "nodes", "tris", "stack")},
                               "frame_ms": frames, "frame_ms_median": statistics.median(frames)}), flush=True)

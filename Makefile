@@ -29,7 +29,8 @@ FLAGS_denoise := -Xclang -target-feature -Xclang -packed-fp32-ops
 FLAGS_wbvh_dev := -Xclang -target-feature -Xclang -packed-fp32-ops
 DEV_OBJ  := $(MAIN_OBJ) $(foreach k,$(STK_CLASSES),$(BUILD)/device/inst_pt_$(k).o $(BUILD)/device/inst_bd_$(k).o)
 CTX_H    := lumo_amd/csrc/device/ctx.h lumo_amd/csrc/host/wbvh.h
-WBDEV_H  := lumo_amd/csrc/device/wbvh_dev.h lumo_amd/csrc/device/wbvh_ploc.h
+WBDEV_H  := lumo_amd/csrc/device/wbvh_dev.h lumo_amd/csrc/device/wbvh_ploc.h \
+            lumo_amd/csrc/device/wbvh_treelet.h
 DEV_H    := $(filter-out $(CTX_H) $(WBDEV_H),$(wildcard lumo_amd/csrc/device/*.h))
 COMMON_H := $(wildcard lumo_amd/csrc/common/*.h) include/lumo_amd.h include/lumo_host.h
 

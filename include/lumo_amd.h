@@ -864,6 +864,56 @@ typedef struct {
 /* Of the last upload.  LUMO_ERR_NO_SCENE before one. */
 lumo_status lumo_scene_wide_cluster_info(void* ctx, lumo_wide_cluster_info* info);
 
+/* ---------------------------------------------------------------------------------
+ * Treelet restructuring of the clustered tree (after Karras & Aila 2013, section 3).  A third
+ * per-context setting, read by the next upload; it acts only when the device builder ran with a
+ * cluster radius >= 1 and is inert otherwise (the LBVH, the host builder, a refused device build,
+ * accel = 0: passes_used, the counts and the areas are then 0).  An addition within ABI 10, found by
+ * dlsym.  Between 5' and 5'' (f64; every choice determined; the only atomics are integer counters):
+ *   5t treelets  The objective is the sum of the half-area of the box over the internal binary nodes
+ *               (half-area as in 5'; a NaN area counts as +inf here throughout); a primitive or an
+ *               object leaf costs nothing.  `passes` passes run, each bottom-up: a node is handled
+ *               when both of its child subtrees are finished, and the treelets of unrelated nodes
+ *               are disjoint subtrees, so the result does not depend on timing.  gamma is the same
+ *               in every pass.  At a node R whose subtree holds gamma primitives or more:
+ *               (a) Treelet.  Its leaves are R's two children; while fewer than 7, the leaf of
+ *               largest half-area that is an internal node is replaced in place by its two children
+ *               (the first in treelet order on ties).  Fewer than 7 leaves in the end: R is skipped.
+ *               (b) Optimal topology.  For each of the 127 non-empty subsets S of the 7 leaves a(S)
+ *               is the half-area of the union box, formed in ascending leaf order; c(S) = 0 for a
+ *               single leaf, else c(S) = a(S) + min over the proper non-empty P in S that hold the
+ *               lowest leaf of S of (c(P) + c(S \ P)), the numerically smallest P on ties.
+ *               (c) Replace only if c(all) is strictly below the cost of the present topology,
+ *               summed the same way (a(S) + (cost of one child + cost of the other) at each of its 6
+ *               internal nodes, S the node's leaves): the present topology is one of the candidates
+ *               of (b), so an equal cost never replaces.  The new internal nodes are the sets of the
+ *               optimal topology in pre-order (a node, then its part P, then S \ P); they take the
+ *               6 old slots in the order R, then the others as (a) opened them, so R keeps its slot
+ *               and a tree's root stays at its base.  Each node's children are (P, S \ P); children,
+ *               parent links (the 7 leaves' too), union box (ascending leaf order), primitive count
+ *               and "holds an object leaf" of the 6 slots are rewritten.
+ * area_before and area_after are the objective over all trees before the first pass and after the
+ * last, each reduced in a fixed order; with passes = 0 both are the objective of the clustered tree.
+ * ------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t passes;   /* 0 (default): off.  1 .. 8 */
+    int32_t gamma;    /* 0: the built-in value, 7.  7 .. 2^20: least primitives under a restructured node */
+    int32_t reserved[2];  /* 0 */
+} lumo_wide_treelet_cfg;
+/* cfg NULL: the defaults.  LUMO_ERR_INVALID for a NULL context, a field outside its range or a
+ * non-zero reserved; the setting is then as it was. */
+lumo_status lumo_scene_set_wide_treelet(void* ctx, const lumo_wide_treelet_cfg* cfg);
+
+typedef struct {
+    int32_t passes_used, reserved;
+    int64_t tried, replaced;          /* treelets of 7 leaves over all passes; those that were replaced */
+    double area_before, area_after;
+    double treelet_ms;   /* HIP events around the passes; lumo_wide_build_info.build_ms holds them too,
+                            lumo_wide_cluster_info.cluster_ms does not */
+} lumo_wide_treelet_info;
+/* Of the last upload.  LUMO_ERR_NO_SCENE before one. */
+lumo_status lumo_scene_wide_treelet_info(void* ctx, lumo_wide_treelet_info* info);
+
 /* Test hook: the wide BVH of the uploaded scene as it lies on the device, whichever builder made it.
  * Two calls: with only info (8 values: accel on, nodes, leaf records, stack, depth, objects root,
  * lights root, 0) for the sizes, then with the arrays (nodes x 128 B, records x 10 doubles, one

@@ -781,11 +781,12 @@ class Device:
     """One lumo_amd context bound to one GPU (lumo_create)."""
 
     def __init__(self, device=0, wide_build=None, leaf_max=None, stack_limit=None, wide_cluster=None,
-                 cluster_iters=None, **options):
+                 cluster_iters=None, wide_treelet=None, treelet_gamma=None, **options):
         """options: execution options (LUMO_OPT_*).  wide_build ("host" | "device"), leaf_max and
         stack_limit: set_wide_build's, the builder of the wide BVH an upload with accel=1 uses.
         wide_cluster (a search radius; True: set_wide_cluster's default) and cluster_iters:
-        set_wide_cluster's, the clustered device builder; None: the LBVH."""
+        set_wide_cluster's, the clustered device builder; None: the LBVH.  wide_treelet (passes) and
+        treelet_gamma: set_wide_treelet's, the restructuring passes over the clustered tree; None: off."""
         L = lib()
         ctx = C.c_void_p()
         st = L.lumo_create(device, C.byref(ctx))
@@ -801,6 +802,24 @@ class Device:
             self.set_wide_cluster(max_iter=cluster_iters)
         elif (wide_cluster, cluster_iters) != (None, None):
             self.set_wide_cluster(wide_cluster or 0, max_iter=cluster_iters)
+        if (wide_treelet, treelet_gamma) != (None, None):
+            self.set_wide_treelet(wide_treelet or 0, gamma=treelet_gamma)
+
+    def set_wide_treelet(self, passes=_ffi.WIDE_TREELET_PASSES, gamma=None):
+        """lumo_scene_set_wide_treelet: restructuring passes over the clustered device builder's binary
+        tree at the next upload: every treelet of 7 leaves under a node of `gamma`
+        primitives or more (7..2^20; None: 7) takes the topology of least summed surface area.
+        passes 1..8; 0: off.  Inert unless the device builder runs with a cluster radius."""
+        cfg = _ffi.WideTreeletCfg(passes=int(passes), gamma=0 if gamma is None else int(gamma))
+        check(lib().lumo_scene_set_wide_treelet(self.ctx, C.byref(cfg)), "set_wide_treelet")
+        return self
+
+    def wide_treelet_info(self):
+        """lumo_scene_wide_treelet_info of the last upload, as a dict: passes_used (0: no pass ran), tried,
+        replaced, area_before, area_after, treelet_ms."""
+        info = _ffi.WideTreeletInfo()
+        check(lib().lumo_scene_wide_treelet_info(self.ctx, C.byref(info)), "wide_treelet_info")
+        return {k: getattr(info, k) for k, _ in _ffi.WideTreeletInfo._fields_ if k != "reserved"}
 
     def set_wide_cluster(self, radius=_ffi.WIDE_CLUSTER_RADIUS, max_iter=None):
         """lumo_scene_set_wide_cluster: how the device builder makes its binary tree at the next upload

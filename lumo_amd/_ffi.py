@@ -275,6 +275,20 @@ class WideClusterInfo(C.Structure):
 # Device.set_wide_cluster's default search radius: the best C2 / C3 geometric-mean short frame of
 # DESIGN.md §4g's table (lumo_wide_cluster_cfg's own default is 0: the LBVH)
 WIDE_CLUSTER_RADIUS = 32
+
+
+class WideTreeletCfg(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("gamma", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class WideTreeletInfo(C.Structure):
+    _fields_ = [("passes_used", C.c_int32), ("reserved", C.c_int32), ("tried", C.c_int64), ("replaced", C.c_int64),
+                ("area_before", C.c_double), ("area_after", C.c_double), ("treelet_ms", C.c_double)]
+
+
+# Device.set_wide_treelet's default pass count: the best C2 / C3 geometric-mean short frame of DESIGN.md
+# §4g's table under "Treelet restructuring" (lumo_wide_treelet_cfg's own default is 0: off)
+WIDE_TREELET_PASSES = 2
 # wide BVH node (csrc/common/wbvh.h Node, 128 B) as lumo_debug_wide_export returns it
 WNODE = [("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("ref", "<i4", 4), ("n", "<i4"), ("pad", "<i4", 3)]
 
@@ -328,6 +342,8 @@ DEVICE_API = [
     ("lumo_scene_wide_build_info", C.c_int32, [C.c_void_p, C.POINTER(WideBuildInfo)]),
     ("lumo_scene_set_wide_cluster", C.c_int32, [C.c_void_p, C.POINTER(WideClusterCfg)]),
     ("lumo_scene_wide_cluster_info", C.c_int32, [C.c_void_p, C.POINTER(WideClusterInfo)]),
+    ("lumo_scene_set_wide_treelet", C.c_int32, [C.c_void_p, C.POINTER(WideTreeletCfg)]),
+    ("lumo_scene_wide_treelet_info", C.c_int32, [C.c_void_p, C.POINTER(WideTreeletInfo)]),
     ("lumo_debug_wide_export", C.c_int32, [C.c_void_p, c_int64_p, C.c_void_p, c_double_p, c_int32_p, c_int32_p]),
 ]
 HOST_API = [

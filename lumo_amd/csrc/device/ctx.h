@@ -166,6 +166,9 @@ struct Ctx {
     // how the device builder makes its binary tree (lumo_scene_set_wide_cluster), and what the last upload did
     lumo_wide_cluster_cfg wc_cfg{};
     lumo_wide_cluster_info wc_info{};
+    // the treelet passes over the clustered tree (lumo_scene_set_wide_treelet), and what the last upload did
+    lumo_wide_treelet_cfg wt_cfg{};
+    lumo_wide_treelet_info wt_info{};
 };
 
 lumo_status dev_alloc(const Ctx& c, DevBuf& b, size_t bytes);
@@ -183,6 +186,7 @@ struct WideDev {
     double sah = 0.0, ms = 0.0;
     std::vector<int32_t> root_ref;  // per tree of the DevPrep
     lumo_wide_cluster_info cluster{};  // zeros: the LBVH
+    lumo_wide_treelet_info treelet{};  // zeros: the LBVH
 };
 lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangles, WideDev& out);
 void wide_dev_free(WideDev& wd);

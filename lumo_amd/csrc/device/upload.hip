@@ -313,6 +313,7 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
     c->wb_info.builder_asked = c->wb_cfg.builder;
     c->wb_info.builder_used = -1;
     c->wc_info = lumo_wide_cluster_info{};
+    c->wt_info = lumo_wide_treelet_info{};
     auto fetch_wide = [&](size_t nodes, bool records) {
         if (dev_built && acc.nodes.size() < nodes) {
             acc.nodes.resize(nodes);
@@ -351,6 +352,7 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
             c->wb_info.sah_cost = wd.sah;
             c->wb_info.levels = wd.levels;
             c->wc_info = wd.cluster;
+            c->wt_info = wd.treelet;
             c->wb_info.trees = (int)std::count_if(wd.root_ref.begin(), wd.root_ref.end(),
                                                   [](int32_t r) { return r != wbvh::NONE; });
         } else {

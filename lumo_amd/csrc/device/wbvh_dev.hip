@@ -1,6 +1,7 @@
-// Device builder of the wide BVH: the launches of the kernels of wbvh_dev.h and
-// wbvh_ploc.h, and the entry points lumo_scene_set_wide_build, lumo_scene_wide_build_info,
-// lumo_scene_set_wide_cluster, lumo_scene_wide_cluster_info and lumo_debug_wide_export.
+// Device builder of the wide BVH: the launches of the kernels of wbvh_dev.h,
+// wbvh_ploc.h and wbvh_treelet.h, and the entry points lumo_scene_set_wide_build,
+// lumo_scene_wide_build_info, lumo_scene_set_wide_cluster, lumo_scene_wide_cluster_info,
+// lumo_scene_set_wide_treelet, lumo_scene_wide_treelet_info and lumo_debug_wide_export.
 // lumo_scene_upload (upload.hip) calls wide_build_device when the context asks for this builder.
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 #include "ctx.h"
 #include "wbvh_dev.h"
 #include "wbvh_ploc.h"
+#include "wbvh_treelet.h"
 
 using namespace lumo;
 using namespace lumo::dev;
@@ -55,11 +57,11 @@ inline int blocks(size_t n) { return (int)((n + WB_BLOCK - 1) / WB_BLOCK); }
     } while (0)
 
 struct Events {
-    hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr;  // the build; its clustering
+    hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr, e = nullptr, f = nullptr;  // the build; its clustering; its treelet passes
     uint32_t* pinned = nullptr;
     ~Events() {
-        for (hipEvent_t e : {a, b, c, d})
-            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t x : {a, b, c, d, e, f})
+            if (x) (void)hipEventDestroy(x);
         if (pinned) (void)hipHostFree(pinned);
     }
 };
@@ -98,6 +100,8 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
     HIPCHK(hipEventCreate(&ev.b));
     HIPCHK(hipEventCreate(&ev.c));
     HIPCHK(hipEventCreate(&ev.d));
+    HIPCHK(hipEventCreate(&ev.e));
+    HIPCHK(hipEventCreate(&ev.f));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ev.pinned), sizeof(uint32_t) * 2));
     WbWork w{};
     w.n_prims = (int32_t)N;
@@ -141,6 +145,9 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
     // their scan take the key buffers, which nobody reads after the sort, the relabelled idx the spare one
     PlWork pl{};
     uint32_t* pl_sums = nullptr;
+    TlStat* tl_stat = nullptr;
+    double* tl_part = nullptr;
+    const int tl_passes = c.wt_cfg.passes, tl_gamma = c.wt_cfg.gamma > 0 ? c.wt_cfg.gamma : TL_GAMMA;
     pl.radius = c.wc_cfg.radius;
     if (pl.radius > 0) {
         for (int k = 0; k < 2; ++k) {
@@ -153,6 +160,10 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
         WB_TRY(ws.get(c, &pl.nn, N));
         WB_TRY(ws.get(c, &pl.lpar, N));
         WB_TRY(ws.get(c, &pl_sums, (size_t)scan_blocks((uint32_t)(2 * N))));
+        // the treelet passes (wbvh_treelet.h) need nothing per primitive: their arrival counters are
+        // w.iflag, which only the LBVH's fit uses before the collapse
+        WB_TRY(ws.get(c, &tl_stat, 1));
+        WB_TRY(ws.get(c, &tl_part, (size_t)WB_STAT_GRID));
     }
     WB_TRY(dev_alloc(c, out.tv, sizeof(double) * wbvh::TV * (size_t)prep.n_tris));
     w.tv = static_cast<double*>(out.tv.p);
@@ -215,6 +226,21 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
             (nearest ? out.cluster.iterations : out.cluster.paired_iterations)++;
             n -= merged;
             pc ^= 1;
+        }
+        // 5t. the objective, and the treelet passes over the finished binary tree (gamma stays)
+        const int ag = std::min(nb, WB_STAT_GRID);
+        k_wb_fill<<<1, WB_BLOCK, 0, sm>>>(reinterpret_cast<uint32_t*>(tl_stat), 0u, (uint32_t)(sizeof(TlStat) / 4));
+        k_tl_area_partial<<<ag, WB_BLOCK, 0, sm>>>(w, tl_part);
+        k_tl_area_final<<<1, WB_BLOCK, 0, sm>>>(ag, tl_part, tl_stat, 0);
+        if (tl_passes > 0) {
+            HIPCHK(hipEventRecord(ev.e, sm));
+            for (int p = 0; p < tl_passes; ++p) {
+                k_wb_fill<<<nb, WB_BLOCK, 0, sm>>>(w.iflag, 0u, (uint32_t)N);
+                k_tl_pass<<<(int)((N + TL_BLOCK - 1) / TL_BLOCK), TL_BLOCK, 0, sm>>>(w, pl, tl_gamma, tl_stat);
+            }
+            HIPCHK(hipEventRecord(ev.f, sm));
+            k_tl_area_partial<<<ag, WB_BLOCK, 0, sm>>>(w, tl_part);
+            k_tl_area_final<<<1, WB_BLOCK, 0, sm>>>(ag, tl_part, tl_stat, 1);
         }
         k_pl_order<<<nb, WB_BLOCK, 0, sm>>>(w, pl);
         HIPCHK(hipEventRecord(ev.d, sm));
@@ -299,6 +325,19 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
     if (pl.radius > 0) {
         float cms = 0.0f;
         HIPCHK(hipEventElapsedTime(&cms, ev.c, ev.d));
+        TlStat ts{};
+        HIPCHK(hipMemcpy(&ts, tl_stat, sizeof(ts), hipMemcpyDeviceToHost));
+        out.treelet.area_before = ts.area[0];
+        out.treelet.area_after = ts.area[tl_passes > 0 ? 1 : 0];
+        if (tl_passes > 0) {
+            float tms = 0.0f;
+            HIPCHK(hipEventElapsedTime(&tms, ev.e, ev.f));
+            out.treelet.passes_used = tl_passes;
+            out.treelet.tried = (int64_t)ts.tried;
+            out.treelet.replaced = (int64_t)ts.replaced;
+            out.treelet.treelet_ms = (double)tms;
+            cms -= tms;  // the passes lie between the last merge and the relabel
+        }
         out.cluster.cluster_ms = (double)cms;
     }
     WbScal sc{};
@@ -355,6 +394,25 @@ lumo_status lumo_scene_wide_cluster_info(void* ctx, lumo_wide_cluster_info* info
     if (!c || !info) return LUMO_ERR_INVALID;
     if (!c->has_scene) return LUMO_ERR_NO_SCENE;
     *info = c->wc_info;
+    return LUMO_OK;
+}
+
+lumo_status lumo_scene_set_wide_treelet(void* ctx, const lumo_wide_treelet_cfg* cfg) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c) return LUMO_ERR_INVALID;
+    const lumo_wide_treelet_cfg v = cfg ? *cfg : lumo_wide_treelet_cfg{};
+    if (v.passes < 0 || v.passes > TL_PASSES_MAX || (v.gamma != 0 && (v.gamma < TL_LEAVES || v.gamma > TL_GAMMA_MAX)) ||
+        v.reserved[0] != 0 || v.reserved[1] != 0)
+        return LUMO_ERR_INVALID;
+    c->wt_cfg = v;
+    return LUMO_OK;
+}
+
+lumo_status lumo_scene_wide_treelet_info(void* ctx, lumo_wide_treelet_info* info) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !info) return LUMO_ERR_INVALID;
+    if (!c->has_scene) return LUMO_ERR_NO_SCENE;
+    *info = c->wt_info;
     return LUMO_OK;
 }
 

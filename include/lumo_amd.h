@@ -914,6 +914,49 @@ typedef struct {
 /* Of the last upload.  LUMO_ERR_NO_SCENE before one. */
 lumo_status lumo_scene_wide_treelet_info(void* ctx, lumo_wide_treelet_info* info);
 
+/* ---------------------------------------------------------------------------------
+ * Dynamic geometry: vertices updated in place, the wide BVH refit on the device (DESIGN.md §4g
+ * "Refit").  Additions within ABI 10, found by dlsym.
+ *
+ * lumo_scene_update_vertices overwrites vertices first .. first + count - 1 of the uploaded scene
+ * with xyz (3 * count doubles) and brings everything the wide mode (accel = 1) reads up to date: the
+ * per-triangle soup, the leaf records, the child boxes of every node of every tree (world objects,
+ * world lights, each BLAS), the world boxes of the instance leaves (from the exact f64 bounds of
+ * their BLAS, through the builders' transform rule), max_abs and the staged LDS copies.  The
+ * topology (refs, child counts, record order, roots, stack need, depth) stays.  A child box is
+ * again the f32 box rounded outward from the exact f64 bounds of what lies beneath it, so a refit
+ * tree walks like any valid tree; it is only as good a partition as the moved geometry lets the old
+ * topology be (compare sah_cost with sah_build and rebuild with lumo_scene_upload when it has grown).
+ * Works on a tree of either builder, with any cluster / treelet setting.  Synchronous.
+ *
+ * Refused, with nothing modified:
+ *   LUMO_ERR_INVALID      NULL ctx or xyz, first < 0, count < 0, first + count > the scene's vertices,
+ *                         a non-finite coordinate
+ *   LUMO_ERR_NO_SCENE     before an upload
+ *   LUMO_ERR_UNSUPPORTED  the scene's lumo_scene_info.accel is 0 (kd-trees and object BVHs cannot be
+ *                         refit); a protected vertex given a value not bit-equal to its present one
+ * A vertex is protected when a triangle of a light, or of an object that is no kd mesh (a Rectangle,
+ * a single Triangle), uses it: the sampled light's own hit walks that light's kd-tree, and areas,
+ * Rectangle parameters and the alias table are made on the host.  Values bit-equal to the present
+ * ones are always accepted, so the whole vertex array of the moved scene may be passed.
+ * Normals and uvs are not touched.
+ * ------------------------------------------------------------------------------- */
+lumo_status lumo_scene_update_vertices(void* ctx, int32_t first, int32_t count, const double* xyz);
+
+typedef struct {
+    int64_t changed;   /* vertices of the last accepted update whose value changed                      */
+    int64_t updates;   /* accepted updates since the upload (0: the other fields but sah_build are 0)  */
+    double refit_ms;   /* HIP events around the device work of the last update                         */
+    double sah_cost;   /* after the last update, by lumo_wide_build_info.sah_cost's rule                */
+    double sah_build;  /* of the tree as it was built, by the device's reduction: lumo_wide_build_info.
+                          sah_cost itself for the device builder, within rounding of it for the host's;
+                          0 before the first update                                                     */
+    float max_abs;     /* the largest |box coordinate| after the last update                           */
+    int32_t reserved;
+} lumo_refit_info;
+/* Of the last accepted update since the upload.  LUMO_ERR_NO_SCENE before an upload. */
+lumo_status lumo_scene_refit_info(void* ctx, lumo_refit_info* info);
+
 /* Test hook: the wide BVH of the uploaded scene as it lies on the device, whichever builder made it.
  * Two calls: with only info (8 values: accel on, nodes, leaf records, stack, depth, objects root,
  * lights root, 0) for the sizes, then with the arrays (nodes x 128 B, records x 10 doubles, one

@@ -876,6 +876,25 @@ class Device:
                     stack=int(info[3]), depth=int(info[4]), obj_root=int(info[5]), light_root=int(info[6]),
                     obj_blas=ob[:no], light_blas=lb[:nl])
 
+    def update_vertices(self, xyz, first=0):
+        """lumo_scene_update_vertices: overwrite vertices first .. first + len(xyz) - 1 of the uploaded
+        scene ((n, 3) float64) and refit the wide BVH on the device (DESIGN.md §4g "Refit"); needs
+        accel=1.  Lights and objects that are no kd mesh must keep their vertices (values equal to the
+        present ones are accepted, so the whole moved array may be passed).  Raises on a refusal; the
+        scene is then as it was."""
+        v = np.ascontiguousarray(xyz, dtype=np.float64)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError("update_vertices: an (n, 3) array expected")
+        check(lib().lumo_scene_update_vertices(self.ctx, int(first), len(v), _dptr(v)), "update_vertices")
+        return self
+
+    def refit_info(self):
+        """lumo_scene_refit_info of the last update since the upload, as a dict: changed (vertices),
+        updates, refit_ms, sah_cost, sah_build (the tree as built, by the same reduction), max_abs."""
+        info = _ffi.RefitInfo()
+        check(lib().lumo_scene_refit_info(self.ctx, C.byref(info)), "refit_info")
+        return {k: getattr(info, k) for k, _ in _ffi.RefitInfo._fields_ if k != "reserved"}
+
     def upload(self, scene, camera=None):
         L = lib()
         self._scene_desc = scene.desc()

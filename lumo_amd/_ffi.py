@@ -289,6 +289,13 @@ class WideTreeletInfo(C.Structure):
 # Device.set_wide_treelet's default pass count: the best C2 / C3 geometric-mean short frame of DESIGN.md
 # §4g's table under "Treelet restructuring" (lumo_wide_treelet_cfg's own default is 0: off)
 WIDE_TREELET_PASSES = 2
+
+
+class RefitInfo(C.Structure):
+    _fields_ = [("changed", C.c_int64), ("updates", C.c_int64), ("refit_ms", C.c_double), ("sah_cost", C.c_double),
+                ("sah_build", C.c_double), ("max_abs", C.c_float), ("reserved", C.c_int32)]
+
+
 # wide BVH node (csrc/common/wbvh.h Node, 128 B) as lumo_debug_wide_export returns it
 WNODE = [("lo", "<f4", (3, 4)), ("hi", "<f4", (3, 4)), ("ref", "<i4", 4), ("n", "<i4"), ("pad", "<i4", 3)]
 
@@ -345,6 +352,8 @@ DEVICE_API = [
     ("lumo_scene_set_wide_treelet", C.c_int32, [C.c_void_p, C.POINTER(WideTreeletCfg)]),
     ("lumo_scene_wide_treelet_info", C.c_int32, [C.c_void_p, C.POINTER(WideTreeletInfo)]),
     ("lumo_debug_wide_export", C.c_int32, [C.c_void_p, c_int64_p, C.c_void_p, c_double_p, c_int32_p, c_int32_p]),
+    ("lumo_scene_update_vertices", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_double_p]),
+    ("lumo_scene_refit_info", C.c_int32, [C.c_void_p, C.POINTER(RefitInfo)]),
 ]
 HOST_API = [
     ("lumo_spectrum_from_rgb", Spectrum, [C.c_double, C.c_double, C.c_double]),

@@ -105,6 +105,21 @@ struct Opts {
     int64_t accel = 0;                 // upload: 0 lumo's BVHs + kd-trees, 1 the wide BVH (wbvh.h)
 };
 
+// lumo_scene_update_vertices (wbvh_dev.hip, wbvh_refit.h): what the first update after an upload makes
+// and the later ones reuse.  The buffers are the scene's (scene_bufs); free_scene resets this.
+struct Refit {
+    bool ready = false;
+    uint8_t* prot = nullptr;    // per vertex: of a light, or of an object that is no kd mesh
+    double* vnew = nullptr;     // the values of an update until they are accepted
+    uint32_t* flags = nullptr;  // RF_FLAGS words of k_rf_stage_vertices
+    int32_t *parent = nullptr, *wtree = nullptr;  // per node
+    uint32_t *kids = nullptr, *arrive = nullptr;
+    double *box = nullptr, *rarea = nullptr, *psum = nullptr;
+    float* pmax = nullptr;
+    void* scal = nullptr;  // WbScal
+    lumo_refit_info info{};
+};
+
 struct Ctx {
     int device = 0;
     size_t lds_cu = 160 * 1024;     // LDS per CU (hipDeviceProp_t::maxSharedMemoryPerMultiProcessor)
@@ -169,6 +184,8 @@ struct Ctx {
     // the treelet passes over the clustered tree (lumo_scene_set_wide_treelet), and what the last upload did
     lumo_wide_treelet_cfg wt_cfg{};
     lumo_wide_treelet_info wt_info{};
+    int n_vertices = 0, n_triangles = 0;  // of the uploaded scene (lumo_scene_update_vertices)
+    Refit rf;
 };
 
 lumo_status dev_alloc(const Ctx& c, DevBuf& b, size_t bytes);

@@ -43,6 +43,7 @@ void free_scene(Ctx& c) {
     for (DevBuf& b : c.scene_bufs)
         if (b.p) (void)hipFree(b.p);
     c.scene_bufs.clear();
+    c.rf = Refit{};
     c.has_scene = false;
 }
 

@@ -618,6 +618,8 @@ lumo_status lumo_scene_upload(void* ctx, const lumo_scene_desc* d) {
         free_scene(*c);
         return st;
     }
+    c->n_vertices = d->num_vertices;
+    c->n_triangles = d->num_triangles;
     c->has_scene = true;
     return LUMO_OK;
 }

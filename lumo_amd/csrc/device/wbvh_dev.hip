@@ -3,6 +3,8 @@
 // lumo_scene_wide_build_info, lumo_scene_set_wide_cluster, lumo_scene_wide_cluster_info,
 // lumo_scene_set_wide_treelet, lumo_scene_wide_treelet_info and lumo_debug_wide_export.
 // lumo_scene_upload (upload.hip) calls wide_build_device when the context asks for this builder.
+// Also the refit of a tree of either builder after its vertices moved (the kernels of wbvh_refit.h):
+// lumo_scene_update_vertices and lumo_scene_refit_info.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +14,7 @@
 #include "ctx.h"
 #include "wbvh_dev.h"
 #include "wbvh_ploc.h"
+#include "wbvh_refit.h"
 #include "wbvh_treelet.h"
 
 using namespace lumo;
@@ -357,7 +360,186 @@ lumo_status wide_build_device(Ctx& c, const wbvh::DevPrep& prep, int num_triangl
 }  // namespace dev
 }  // namespace lumo
 
+namespace {
+
+// ---------------------------------------------------------------- refit (wbvh_refit.h)
+template <typename T>
+lumo_status rf_get(Ctx& c, T** p, size_t count) {
+    c.scene_bufs.emplace_back();
+    const lumo_status st = dev_alloc(c, c.scene_bufs.back(), sizeof(T) * std::max<size_t>(count, 1));
+    *p = static_cast<T*>(c.scene_bufs.back().p);
+    return st;
+}
+
+RfWork rf_work(const Ctx& c) {
+    const DScene& s = c.sc;
+    const Refit& r = c.rf;
+    RfWork w{};
+    w.n_nodes = c.w_nodes;
+    w.n_recs = c.w_tris;
+    w.n_lights = s.n_lights;
+    w.n_objs = s.n_objs;
+    w.oroot = s.w_oroot;
+    w.lroot = s.w_lroot;
+    w.vertices = s.vertices;
+    w.tris = s.tris;
+    w.objs = s.objs;
+    w.lights = s.lights;
+    w.xforms = s.xforms;
+    w.oblas = s.w_oblas;
+    w.lblas = s.w_lblas;
+    w.nodes = const_cast<wbvh::Node*>(s.wnodes);
+    w.wtv = const_cast<double*>(s.wtv);
+    w.soup = const_cast<double*>(s.tv);
+    w.parent = r.parent;
+    w.kids = r.kids;
+    w.arrive = r.arrive;
+    w.wtree = r.wtree;
+    w.box = reinterpret_cast<WbBox*>(r.box);
+    w.rarea = r.rarea;
+    return w;
+}
+
+// max_abs and the SAH cost of the nodes as they lie, by the builder's reductions; leaves them in scal
+void rf_stats(const Ctx& c, const RfWork& w, hipStream_t sm) {
+    if (w.n_nodes <= 0) return;
+    WbWork b{};
+    b.nodes = w.nodes;
+    b.wtree = w.wtree;
+    b.scal = static_cast<WbScal*>(c.rf.scal);
+    const int grid = std::min(blocks((size_t)w.n_nodes), WB_STAT_GRID);
+    k_rf_rootarea<<<blocks((size_t)w.n_nodes), WB_BLOCK, 0, sm>>>(w);
+    k_wb_stats_partial<<<grid, WB_BLOCK, 0, sm>>>(b, w.n_nodes, w.rarea, c.rf.pmax, c.rf.psum);
+    k_wb_stats_final<<<1, WB_BLOCK, 0, sm>>>(b, grid, c.rf.pmax, c.rf.psum);
+}
+
+lumo_status rf_read_scal(const Ctx& c, hipStream_t sm, WbScal* sc) {
+    *sc = WbScal{};
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(sm));
+    if (c.w_nodes > 0) HIPCHK(hipMemcpy(sc, c.rf.scal, sizeof(*sc), hipMemcpyDeviceToHost));
+    return LUMO_OK;
+}
+
+// the first update after an upload: the workspace (72 B per node, 25 B per vertex), the protected
+// vertices, the parent links and the cost of the tree as built
+lumo_status rf_init(Ctx& c) {
+    Refit& r = c.rf;
+    const size_t nv = (size_t)c.n_vertices, nn = (size_t)c.w_nodes;
+    uint32_t* prot32 = nullptr;
+    WbScal* scal = nullptr;
+    WB_TRY(rf_get(c, &prot32, (nv + 3) / 4));
+    WB_TRY(rf_get(c, &r.vnew, 3 * nv));
+    WB_TRY(rf_get(c, &r.flags, (size_t)RF_FLAGS));
+    WB_TRY(rf_get(c, &r.parent, nn));
+    WB_TRY(rf_get(c, &r.wtree, nn));
+    WB_TRY(rf_get(c, &r.kids, nn));
+    WB_TRY(rf_get(c, &r.arrive, nn));
+    WB_TRY(rf_get(c, &r.box, 6 * nn));
+    WB_TRY(rf_get(c, &r.rarea, nn));
+    WB_TRY(rf_get(c, &r.pmax, (size_t)WB_STAT_GRID));
+    WB_TRY(rf_get(c, &r.psum, (size_t)WB_STAT_GRID));
+    WB_TRY(rf_get(c, &scal, 1));
+    r.prot = reinterpret_cast<uint8_t*>(prot32);
+    r.scal = scal;
+    hipStream_t sm = c.streams[0];
+    const RfWork w = rf_work(c);
+    if (nv > 0) k_wb_fill<<<blocks((nv + 3) / 4), WB_BLOCK, 0, sm>>>(prot32, 0u, (uint32_t)((nv + 3) / 4));
+    if (w.n_lights + w.n_objs > 0)
+        k_rf_protect<<<w.n_lights + w.n_objs, WB_BLOCK, 0, sm>>>(w, c.n_vertices, c.n_triangles, r.prot);
+    if (nn > 0) {
+        k_wb_fill<<<blocks(nn), WB_BLOCK, 0, sm>>>(reinterpret_cast<uint32_t*>(r.parent), ~0u, (uint32_t)nn);
+        k_rf_parents<<<blocks(nn), WB_BLOCK, 0, sm>>>(w);
+        k_rf_trees<<<blocks(nn), WB_BLOCK, 0, sm>>>(w);
+        rf_stats(c, w, sm);
+    }
+    WbScal sc;
+    WB_TRY(rf_read_scal(c, sm, &sc));
+    r.info = lumo_refit_info{};
+    r.info.sah_build = sc.sah;
+    r.ready = true;
+    return LUMO_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+lumo_status lumo_scene_update_vertices(void* ctx, int32_t first, int32_t count, const double* xyz) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !xyz) return LUMO_ERR_INVALID;
+    if (!c->has_scene) return LUMO_ERR_NO_SCENE;
+    if (!c->sc.accel) return LUMO_ERR_UNSUPPORTED;
+    if (first < 0 || count < 0 || (int64_t)first + count > c->n_vertices) return LUMO_ERR_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->rf.ready) WB_TRY(rf_init(*c));
+    Refit& r = c->rf;
+    DScene& s = c->sc;
+    hipStream_t sm = c->streams[0];
+    Events ev;
+    HIPCHK(hipEventCreate(&ev.a));
+    HIPCHK(hipEventCreate(&ev.b));
+    const size_t n3 = 3 * (size_t)count;
+    if (count > 0) HIPCHK(hipMemcpy(r.vnew, xyz, sizeof(double) * n3, hipMemcpyHostToDevice));
+    HIPCHK(hipEventRecord(ev.a, sm));
+    // 1. the new values against the present ones: one read-back decides
+    uint32_t flags[RF_FLAGS] = {};
+    k_wb_fill<<<1, WB_BLOCK, 0, sm>>>(r.flags, 0u, (uint32_t)RF_FLAGS);
+    if (count > 0) {
+        k_rf_stage_vertices<<<blocks((size_t)count), WB_BLOCK, 0, sm>>>(r.vnew, s.vertices, r.prot, first, count, r.flags);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(sm));
+        HIPCHK(hipMemcpy(flags, r.flags, sizeof(flags), hipMemcpyDeviceToHost));
+    }
+    if (flags[RF_NONFINITE]) return LUMO_ERR_INVALID;
+    if (flags[RF_PROTECTED]) return LUMO_ERR_UNSUPPORTED;
+    if (count > 0)
+        HIPCHK(hipMemcpyAsync(const_cast<double*>(s.vertices) + 3 * (size_t)first, r.vnew, sizeof(double) * n3,
+                              hipMemcpyDeviceToDevice, sm));
+    // 2. records and soup  3. boxes: the BLASes, then the world trees  4. max_abs, cost, staged sets
+    const RfWork w = rf_work(*c);
+    if (w.n_recs > 0) k_rf_records<<<blocks((size_t)w.n_recs), WB_BLOCK, 0, sm>>>(w);
+    if (w.n_nodes > 0) {
+        const int grid = (w.n_nodes + RF_QUADS - 1) / RF_QUADS;
+        k_wb_fill<<<blocks((size_t)w.n_nodes), WB_BLOCK, 0, sm>>>(r.arrive, 0u, (uint32_t)w.n_nodes);
+        k_rf_fit<<<grid, WB_BLOCK, 0, sm>>>(w, 0);
+        k_rf_fit<<<grid, WB_BLOCK, 0, sm>>>(w, 1);
+        rf_stats(*c, w, sm);
+    }
+    auto restage = [&](const char* set, uint32_t off, const void* src, size_t bytes) {
+        const size_t n16 = bytes / 16;  // rows of 80 B, nodes of 128 B
+        if (n16 == 0) return;
+        k_rf_copy<<<std::min(blocks(n16), WB_STAT_GRID), WB_BLOCK, 0, sm>>>(
+            reinterpret_cast<uint4*>(const_cast<char*>(set) + off), static_cast<const uint4*>(src), n16);
+    };
+    if (s.hot_bytes > 0) {
+        restage(s.hot, s.off_tv, s.tv, sizeof(double) * TV_STRIDE * (size_t)c->n_triangles);
+        restage(s.hot, s.off_wnodes, s.wnodes, sizeof(wbvh::Node) * (size_t)w.n_nodes);
+        restage(s.hot, s.off_wtv, s.wtv, sizeof(double) * wbvh::TV * (size_t)w.n_recs);
+    }
+    if (s.top_bytes > 0 && s.top_wnodes > 0)
+        restage(s.top, s.off_top_wnodes, s.wnodes, sizeof(wbvh::Node) * (size_t)s.top_wnodes);
+    HIPCHK(hipEventRecord(ev.b, sm));
+    WbScal sc;
+    WB_TRY(rf_read_scal(*c, sm, &sc));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    s.w_maxabs = (double)sc.max_abs;  // the kernels take DScene by value at every launch
+    r.info.changed = (int64_t)flags[RF_CHANGED];
+    r.info.updates++;
+    r.info.refit_ms = (double)ms;
+    r.info.sah_cost = sc.sah;
+    r.info.max_abs = sc.max_abs;
+    return LUMO_OK;
+}
+
+lumo_status lumo_scene_refit_info(void* ctx, lumo_refit_info* info) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !info) return LUMO_ERR_INVALID;
+    if (!c->has_scene) return LUMO_ERR_NO_SCENE;
+    *info = c->rf.info;
+    return LUMO_OK;
+}
 
 lumo_status lumo_scene_set_wide_build(void* ctx, const lumo_wide_build_cfg* cfg) {
     Ctx* c = static_cast<Ctx*>(ctx);

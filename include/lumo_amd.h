@@ -957,6 +957,60 @@ typedef struct {
 /* Of the last accepted update since the upload.  LUMO_ERR_NO_SCENE before an upload. */
 lumo_status lumo_scene_refit_info(void* ctx, lumo_refit_info* info);
 
+/* ---------------------------------------------------------------------------------
+ * Motion: where each film sample's surface point was before the frame's vertex updates, for the
+ * temporal denoiser (DESIGN.md §4g "Motion").  Additions within ABI 10, found by dlsym.
+ *
+ * lumo_scene_motion_mark copies the present vertex array into the context's "previous" vertices
+ * (allocated by the first mark after an upload, dropped by the next upload and by lumo_destroy).
+ * Per frame: mark, any number of lumo_scene_update_vertices calls, the renders.  Before the first
+ * mark the previous vertices are the present ones, so all motion is exactly 0; with accel = 0
+ * nothing can move and it stays 0.  Errors: LUMO_ERR_INVALID (NULL context), LUMO_ERR_NO_SCENE,
+ * LUMO_ERR_OOM.
+ *
+ * Per sample (f64, never contracted, in this order): delta = 0 for a miss, a light, a sphere, a
+ * Rectangle and a single Triangle (lumo_scene_update_vertices protects them).  For a hit on a kd
+ * mesh, triangle tri with vertices A B C (present) and A' B' C' (previous), on the object's local
+ * ray:
+ *   bary         e / det of the accepted triangle test (triangle.rs:131-134)
+ *   xi           (bary.x A + bary.y B) + bary.z C per component: the record's local p bit for bit
+ *   xi'          the same expression of A' B' C'
+ *   delta_local  xi' - xi
+ *   delta        an instance: row r of its local-to-world m as a direction,
+ *                ((m_r0 dx + m_r1 dy) + m_r2 dz) + m_r3 0; else delta_local
+ * so the point's previous world position is p + delta.
+ *   motion_w     sum w delta, sum w: the beauty film's filter weights summed in its order, channel
+ *                3 the beauty tile's sum w bit for bit.  Consumers divide channels 0-2 by depth_w
+ *                channel 1 (sum w hit): the motion averaged over the samples the depth is.
+ * ------------------------------------------------------------------------------- */
+lumo_status lumo_scene_motion_mark(void* ctx);
+typedef struct {
+    double* motion_w; /* 4 doubles per tile pixel, as rgb_w; NULL: skipped */
+} lumo_motion_planes;
+/* Per-sample records of one task, laid out as lumo_feature_dump's; a NULL array is skipped. */
+typedef struct {
+    double* bary;  /* 3 (zeros where delta is 0 by kind) */
+    double* delta; /* 3 */
+} lumo_motion_dump;
+/* lumo_render_features with the motion plane from the same primary rays: `out` (n entries) may be
+ * NULL, the feature planes are then not made; `motion` has n entries.  Errors as
+ * lumo_render_features, with LUMO_ERR_INVALID for a NULL motion. */
+lumo_status lumo_render_features_motion(void* ctx, const lumo_tile_task* tasks, size_t n, const lumo_feature_cfg* cfg,
+                                        lumo_feature_planes* out, const lumo_motion_planes* motion);
+/* Test hook: the per-sample motion records of one task, with the sampler of lumo_debug_set_sampler;
+ * sample for sample those of lumo_debug_features. */
+lumo_status lumo_debug_motion(void* ctx, const lumo_tile_task* task, lumo_motion_dump* dump);
+/* lumo_denoise_temporal with the frame's motion plane (height x width x 4, assembled like the other
+ * planes).  motion_w NULL: lumo_denoise_temporal itself, the same launches and bits.  Else
+ *   step 1 gains  m = motion_w[0..2] / depth_w[1] per component, 0 where depth_w[1] = 0
+ *   step 2 gains  P' = P + m per component
+ *   step 3 uses   P' wherever it used P: c' = xf(world_to_camera', P'), z' from |P' - o'|
+ * and everything after is unchanged.  Errors as lumo_denoise_temporal. */
+lumo_status lumo_denoise_temporal_motion(void* ctx, const lumo_denoise_in* in, const double* motion_w,
+                                         const lumo_camera_desc* camera, const lumo_denoise_cfg* cfg,
+                                         const lumo_temporal_cfg* tcfg, double* rgb_out, double* variance_out,
+                                         lumo_temporal_info* info);
+
 /* Test hook: the wide BVH of the uploaded scene as it lies on the device, whichever builder made it.
  * Two calls: with only info (8 values: accel on, nodes, leaf records, stack, depth, objects root,
  * lights root, 0) for the sizes, then with the arrays (nodes x 128 B, records x 10 doubles, one

@@ -707,13 +707,18 @@ class FeatureFilm:
         self.albedo_w = np.zeros((height, width, 4), dtype=np.float64)  # Σw·albedo_rgb, Σw
         self.normal_w = np.zeros((height, width, 4), dtype=np.float64)  # Σw·n, Σw
         self.depth_w = np.zeros((height, width, 4), dtype=np.float64)   # Σw·t·hit, Σw·hit, 0, Σw
+        self.motion_w = np.zeros((height, width, 4), dtype=np.float64)  # Σw·Δ, Σw (render_features_motion)
 
     def add_tile(self, task, planes):
-        """Adds one task's (albedo_w, normal_w, depth_w) arrays; batches of a tile accumulate."""
+        """Adds one task's (albedo_w, normal_w, depth_w[, motion_w]) arrays; batches of a tile accumulate."""
         x0, y0 = task.px_min[0], task.px_min[1]
         x1, y1 = task.px_max[0], task.px_max[1]
-        for dst, src in zip((self.albedo_w, self.normal_w, self.depth_w), planes):
+        for dst, src in zip((self.albedo_w, self.normal_w, self.depth_w, self.motion_w), planes):
             dst[y0:y1, x0:x1, :] += np.asarray(src, dtype=np.float64).reshape(y1 - y0, x1 - x0, 4)
+
+    def motion(self):
+        """H x W x 3: the mean displacement to the previous frame of the samples that hit, Σw·Δ / Σw·hit."""
+        return self._ratio(self.motion_w[..., :3], self.depth_w[..., 1:2])
 
     @staticmethod
     def _ratio(num, den):
@@ -895,6 +900,12 @@ class Device:
         check(lib().lumo_scene_refit_info(self.ctx, C.byref(info)), "refit_info")
         return {k: getattr(info, k) for k, _ in _ffi.RefitInfo._fields_ if k != "reserved"}
 
+    def motion_mark(self):
+        """lumo_scene_motion_mark: the present vertices become the "previous" ones of the motion
+        feature (DESIGN.md §4g "Motion").  Per frame: motion_mark(), update_vertices(...), the renders."""
+        check(lib().lumo_scene_motion_mark(self.ctx), "motion_mark")
+        return self
+
     def upload(self, scene, camera=None):
         L = lib()
         self._scene_desc = scene.desc()
@@ -971,19 +982,38 @@ class Device:
         """lumo_render_features over `tasks`: per task the (albedo_w, normal_w, depth_w) planes,
         each a flat array of 4 f64 per tile pixel, aligned sample for sample with render_tasks of
         the same tasks and sampler (channel 3 of every plane is that tile's Σw)."""
+        return self._render_features(tasks, max_paths, sampler, True, False)
+
+    def render_features_motion(self, tasks, max_paths=0, sampler=0, features=True):
+        """lumo_render_features_motion over `tasks`: per task (albedo_w, normal_w, depth_w, motion_w)
+        from one trace of the primary rays, or only motion_w when features=False.  motion_w is
+        (Σw·Δ, Σw) with Δ the displacement from a sample's surface point to where it was at the last
+        motion_mark(); divide by depth_w's channel 1 (DESIGN.md §4g "Motion")."""
+        planes = self._render_features(tasks, max_paths, sampler, features, True)
+        return planes if features else [p[0] for p in planes]
+
+    def _render_features(self, tasks, max_paths, sampler, features, motion):
         L = lib()
         n = len(tasks)
         arr = tasks if isinstance(tasks, C.Array) else (_ffi.TileTask * n)(*tasks)
-        out = (_ffi.FeaturePlanes * n)()
+        out, mot = (_ffi.FeaturePlanes * n)(), (_ffi.MotionPlanes * n)()
         planes = []
         if n:  # each plane's tiles back to back in one allocation, as _result_buffers lays out rgb_w
-            ov = np.frombuffer(out, dtype=np.uint64).reshape(n, 3)
-            for k in range(3):
+            ov, mv = np.frombuffer(out, dtype=np.uint64).reshape(n, 3), np.frombuffer(mot, dtype=np.uint64)
+            for k in ([0, 1, 2] if features else []) + ([3] if motion else []):
                 bufs, _, res = self._result_buffers(arr, n)
-                ov[:, k] = np.frombuffer(res, dtype=np.uint64).reshape(n, -1)[:, 0]
+                ptr = np.frombuffer(res, dtype=np.uint64).reshape(n, -1)[:, 0]
+                if k < 3:
+                    ov[:, k] = ptr
+                else:
+                    mv[:] = ptr
                 planes.append(bufs)
         cfg = _ffi.FeatureCfg(int(sampler), int(max_paths))
-        check(L.lumo_render_features(self.ctx, arr, n, C.byref(cfg), out), "render_features")
+        if motion:
+            check(L.lumo_render_features_motion(self.ctx, arr, n, C.byref(cfg), out if features else None, mot),
+                  "render_features_motion")
+        else:
+            check(L.lumo_render_features(self.ctx, arr, n, C.byref(cfg), out), "render_features")
         return list(zip(*planes))
 
     def debug_features(self, task, sampler=0):
@@ -998,6 +1028,20 @@ class Device:
         check(L.lumo_debug_set_sampler(self.ctx, int(sampler)), "debug_set_sampler")
         try:
             check(L.lumo_debug_features(self.ctx, C.byref(task), C.byref(dump)), "debug_features")
+        finally:
+            L.lumo_debug_set_sampler(self.ctx, 0)
+        return bufs
+
+    def debug_motion(self, task, sampler=0):
+        """lumo_debug_motion: per sample of one task "bary" and "delta" ((samples x pixels, 3) each),
+        sample for sample debug_features' records of the same task and sampler."""
+        L = lib()
+        m = (task.px_max[0] - task.px_min[0]) * (task.px_max[1] - task.px_min[1]) * task.samples
+        bufs = {name: np.zeros((m, 3)) for name, _ in _ffi.MotionDump._fields_}
+        dump = _ffi.MotionDump(*(_dptr(bufs[name]) for name, _ in _ffi.MotionDump._fields_))
+        check(L.lumo_debug_set_sampler(self.ctx, int(sampler)), "debug_set_sampler")
+        try:
+            check(L.lumo_debug_motion(self.ctx, C.byref(task), C.byref(dump)), "debug_motion")
         finally:
             L.lumo_debug_set_sampler(self.ctx, 0)
         return bufs
@@ -1037,7 +1081,7 @@ class Device:
                     if film.splats.any() else None)
         return _ffi.DenoiseIn(w, h, *(_dptr(a) for a in keep)), keep, (h, w)
 
-    def denoise_temporal(self, film, features, camera, return_variance=False, info=None, **cfg):
+    def denoise_temporal(self, film, features, camera, return_variance=False, info=None, motion=None, **cfg):
         """lumo_denoise_temporal: Device.denoise with the context's history of its previous call
         reprojected through `camera` (the frame's Camera) and accumulated; the first
         call, and the first after denoise_reset() or a change of size, equals Device.denoise.  `cfg`:
@@ -1045,17 +1089,26 @@ class Device:
         normal_cos_min, depth_rel_max, feedback, stage_lds) by name.  info: a dict that receives
         with_history, without_history, blocks_staged, blocks_direct and stage_ms (the call's device
         times: upload, prepare, reproject, variance, the variance choice, the iterations with the
-        history write in its place, finish, read-back)."""
+        history write in its place, finish, read-back).  motion: None, or the frame's motion plane
+        (H x W x 4, the motion_w tiles of render_features_motion assembled like the feature planes):
+        lumo_denoise_temporal_motion then reprojects each pixel from where its surface point was."""
         args, keep, (h, w) = self._denoise_in("denoise_temporal", film, features, cfg,
                                               {**_ffi.DENOISE_DEFAULTS, **_ffi.TEMPORAL_DEFAULTS})
+        if motion is not None:
+            motion = np.ascontiguousarray(motion, dtype=np.float64)
+            if motion.shape != (h, w, 4):
+                raise ValueError(f"denoise_temporal: motion is {motion.shape}, expected {(h, w, 4)}")
         pick = lambda d: {**d, **{k: v for k, v in cfg.items() if k in d}}  # noqa: E731
         c, t = _ffi.DenoiseCfg(**pick(_ffi.DENOISE_DEFAULTS)), _ffi.TemporalCfg(**pick(_ffi.TEMPORAL_DEFAULTS))
         times = np.zeros(c.iterations + 8) if info is not None else None
         ti = _ffi.TemporalInfo(stage_ms=_dptr(times))
         out = np.zeros((h, w, 3))
         var = np.zeros((h, w)) if return_variance else None
-        check(lib().lumo_denoise_temporal(self.ctx, C.byref(args), C.byref(camera.desc), C.byref(c), C.byref(t), _dptr(out),
-                                          _dptr(var), C.byref(ti)), "denoise_temporal")
+        tail = (C.byref(camera.desc), C.byref(c), C.byref(t), _dptr(out), _dptr(var), C.byref(ti))
+        if motion is None:
+            check(lib().lumo_denoise_temporal(self.ctx, C.byref(args), *tail), "denoise_temporal")
+        else:
+            check(lib().lumo_denoise_temporal_motion(self.ctx, C.byref(args), _dptr(motion), *tail), "denoise_temporal")
         if info is not None:
             info.update({k: getattr(ti, k) for k, _ in _ffi.TemporalInfo._fields_[:4]}, stage_ms=times.tolist())
         return (out, var) if return_variance else out
@@ -1291,15 +1344,22 @@ class Renderer:
             dev.close()
         return film, features, DenoisedFilm(out, film.color_space)
 
-    def render_denoised_sequence(self, cameras, firefly=None, **cfg):
+    def render_denoised_sequence(self, cameras, firefly=None, vertices=None, **cfg):
         """Yields (film, features, denoised) per camera of `cameras` (each with the renderer's camera's
         resolution): render_denoised's frame with that camera, denoised by Device.denoise_temporal on
         one context whose history is reset at the start, so frame k accumulates frames 0 .. k - 1.
         Frame k is rendered with seed (seed + k) mod 2^64 of the renderer's .seed(), which must be
         set.  `cfg`: the fields Device.denoise_temporal takes; firefly: as render_denoised's, set on
-        that context.  The renderer's own camera and seed are as before afterwards."""
+        that context.  The renderer's own camera and seed are as before afterwards.
+        vertices: per frame None or the scene's whole (n, 3) vertex array of that frame (dynamic
+        geometry): the frames are then rendered by one context with the wide BVH
+        (accel=1, path tracer) that marks the previous vertices, updates them, renders beauty, features and
+        motion (features.motion_w) and denoises with the motion plane."""
         if self._seed is None:
             raise ValueError("Renderer.render_denoised_sequence: set .seed()")
+        if vertices is not None:
+            yield from self._moving_sequence(cameras, firefly, vertices, cfg)
+            return
         seed, camera, tone = self._seed, self.camera, self._tone_map
         dev = Device(self._device)
         try:
@@ -1314,4 +1374,29 @@ class Renderer:
                 yield film, features, DenoisedFilm(out, film.color_space)
         finally:
             self._seed, self.camera, self._tone_map = seed, camera, tone
+            dev.close()
+
+    def _moving_sequence(self, cameras, firefly, vertices, cfg):
+        """render_denoised_sequence with `vertices`: one context renders and denoises every frame."""
+        w, h = self.camera.resolution
+        dev = Device(self._device, accel=1)
+        try:
+            dev.upload(self.scene)
+            dev.set_firefly(firefly)
+            for k, (cam, v) in enumerate(zip(cameras, vertices)):
+                check(lib().lumo_camera_set(dev.ctx, C.byref(cam.desc)), "camera set")
+                dev.motion_mark()
+                if v is not None:
+                    dev.update_vertices(v)
+                tasks = make_tasks(w, h, self._samples, (self._seed + k) & 0xFFFFFFFFFFFFFFFF)
+                film = Film(w, h, getattr(cam, "color_space", 1), samples=self._samples,
+                            filter_radius=cam.desc.filter_radius, filter_sigma=cam.desc.filter_sigma)
+                features = FeatureFilm(w, h, film.color_space)
+                for t, b in zip(tasks, dev.render_tasks(tasks, sampler=self._sampler)[0]):
+                    film.add_tile(t, b)
+                for t, planes in zip(tasks, dev.render_features_motion(tasks, sampler=self._sampler)):
+                    features.add_tile(t, planes)
+                out = dev.denoise_temporal(film, features, cam, motion=features.motion_w, **cfg)
+                yield film, features, DenoisedFilm(out, film.color_space)
+        finally:
             dev.close()

@@ -311,6 +311,14 @@ class FeatureDump(C.Structure):
     _fields_ = [(name, c_int32_p if dt == "i4" else c_double_p) for name, dt, _ in FEATURE_DUMP_FIELDS]
 
 
+class MotionPlanes(C.Structure):
+    _fields_ = [("motion_w", c_double_p)]
+
+
+class MotionDump(C.Structure):
+    _fields_ = [("bary", c_double_p), ("delta", c_double_p)]
+
+
 # (name, restype, argtypes) of every exported symbol declared in include/*.h
 DEVICE_API = [
     ("lumo_create", C.c_int32, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -354,6 +362,13 @@ DEVICE_API = [
     ("lumo_debug_wide_export", C.c_int32, [C.c_void_p, c_int64_p, C.c_void_p, c_double_p, c_int32_p, c_int32_p]),
     ("lumo_scene_update_vertices", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, c_double_p]),
     ("lumo_scene_refit_info", C.c_int32, [C.c_void_p, C.POINTER(RefitInfo)]),
+    ("lumo_scene_motion_mark", C.c_int32, [C.c_void_p]),
+    ("lumo_render_features_motion", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.c_size_t, C.POINTER(FeatureCfg),
+                                                C.POINTER(FeaturePlanes), C.POINTER(MotionPlanes)]),
+    ("lumo_debug_motion", C.c_int32, [C.c_void_p, C.POINTER(TileTask), C.POINTER(MotionDump)]),
+    ("lumo_denoise_temporal_motion", C.c_int32, [C.c_void_p, C.POINTER(DenoiseIn), c_double_p, C.POINTER(CameraDesc),
+                                                 C.POINTER(DenoiseCfg), C.POINTER(TemporalCfg), c_double_p, c_double_p,
+                                                 C.POINTER(TemporalInfo)]),
 ]
 HOST_API = [
     ("lumo_spectrum_from_rgb", Spectrum, [C.c_double, C.c_double, C.c_double]),

@@ -186,6 +186,9 @@ struct Ctx {
     lumo_wide_treelet_info wt_info{};
     int n_vertices = 0, n_triangles = 0;  // of the uploaded scene (lumo_scene_update_vertices)
     Refit rf;
+    // the vertices as lumo_scene_motion_mark last saw them (one of scene_bufs; free_scene resets it);
+    // nullptr before the first mark: the present ones
+    double* vprev = nullptr;
 };
 
 lumo_status dev_alloc(const Ctx& c, DevBuf& b, size_t bytes);

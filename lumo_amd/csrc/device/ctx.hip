@@ -44,6 +44,7 @@ void free_scene(Ctx& c) {
         if (b.p) (void)hipFree(b.p);
     c.scene_bufs.clear();
     c.rf = Refit{};
+    c.vprev = nullptr;
     c.has_scene = false;
 }
 

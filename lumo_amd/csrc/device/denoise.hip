@@ -19,8 +19,10 @@ using namespace lumo::dev;
 namespace {
 
 // Device buffers of a call (Ctx::dn_work), grown on demand and kept for the next call.
-// DN_FF_CNT, the firefly clamp's counter, exists only on a context that has the clamp set.
-enum DnBuf { DN_IN_RGB, DN_IN_ALB, DN_IN_NRM, DN_IN_DEP, DN_IN_ADD, DN_PLANES, DN_HIT, DN_OUT, DN_FF_CNT, DN_BUF_COUNT };
+// DN_FF_CNT, the firefly clamp's counter, exists only on a context that has the clamp set; DN_IN_MOT
+// and DN_MOT (the motion plane and k_dn_motion's m) only where lumo_denoise_temporal_motion got a plane.
+enum DnBuf { DN_IN_RGB, DN_IN_ALB, DN_IN_NRM, DN_IN_DEP, DN_IN_ADD, DN_PLANES, DN_HIT, DN_OUT, DN_FF_CNT, DN_IN_MOT, DN_MOT,
+             DN_BUF_COUNT };
 constexpr int DN_NPLANES = 3 + 1 + 1 + 3 + 1 + 2 * 3 + 2;  // the doubles of DnPlanes per pixel
 
 bool fcfg_valid(const lumo_firefly_cfg& f) {
@@ -75,6 +77,7 @@ struct DnCall {
     unsigned pix_blocks;
     hipStream_t sm;
     hipEvent_t ff_ev[2] = {};  // around the firefly clamp, when the context has it set
+    const double* motion_w = nullptr;  // lumo_denoise_temporal_motion's plane (set before alloc)
 
     ~DnCall() {
         for (hipEvent_t e : ff_ev)
@@ -101,10 +104,11 @@ struct DnCall {
         if (c->dn_work.size() < DN_BUF_COUNT) c->dn_work.resize(DN_BUF_COUNT);
         const size_t b[DN_BUF_COUNT] = {32 * n, 32 * n, 32 * n, 32 * n, in->add_rgb ? 24 * n : 0,
                                         sizeof(double) * DN_NPLANES * n, sizeof(uint32_t) * n, 24 * n,
-                                        c->dn_ff_on ? sizeof(unsigned long long) : 0};
+                                        c->dn_ff_on ? sizeof(unsigned long long) : 0, motion_w ? 32 * n : 0,
+                                        motion_w ? 24 * n : 0};
         for (int k = 0; k < DN_BUF_COUNT; ++k) {
             bytes[k] = b[k];
-            if (k == DN_FF_CNT && !b[k]) continue;
+            if (k >= DN_FF_CNT && !b[k]) continue;
             const lumo_status st = dev_alloc(*c, c->dn_work[k], bytes[k]);
             if (st) return st;
         }
@@ -125,6 +129,7 @@ struct DnCall {
         const double* host[5] = {in->rgb_w, in->albedo_w, in->normal_w, in->depth_w, in->add_rgb};
         for (int k = 0; k < 5; ++k)
             if (host[k]) HIPCHK(hipMemcpyAsync(buf(DN_IN_RGB + k), host[k], bytes[DN_IN_RGB + k], hipMemcpyHostToDevice, sm));
+        if (motion_w) HIPCHK(hipMemcpyAsync(buf(DN_IN_MOT), motion_w, bytes[DN_IN_MOT], hipMemcpyHostToDevice, sm));
         return LUMO_OK;
     }
     void prepare() const {
@@ -268,9 +273,18 @@ extern "C" lumo_status lumo_denoise_reset(void* ctx) {
 extern "C" lumo_status lumo_denoise_temporal(void* ctx, const lumo_denoise_in* in, const lumo_camera_desc* camera,
                                              const lumo_denoise_cfg* cfg, const lumo_temporal_cfg* tcfg, double* rgb_out,
                                              double* variance_out, lumo_temporal_info* info) {
+    return lumo_denoise_temporal_motion(ctx, in, nullptr, camera, cfg, tcfg, rgb_out, variance_out, info);
+}
+
+// motion_w == nullptr: lumo_denoise_temporal, launch for launch.
+extern "C" lumo_status lumo_denoise_temporal_motion(void* ctx, const lumo_denoise_in* in, const double* motion_w,
+                                                    const lumo_camera_desc* camera, const lumo_denoise_cfg* cfg,
+                                                    const lumo_temporal_cfg* tcfg, double* rgb_out, double* variance_out,
+                                                    lumo_temporal_info* info) {
     DnCall k;
     lumo_status st = k.open(ctx, in, cfg, rgb_out);
     if (st) return st;
+    k.motion_w = motion_w;
     lumo_temporal_cfg t = {0.2, 0.9, 0.1, 32, 4, 1, 1};
     if (tcfg) t = *tcfg;
     if (!camera || camera->width != in->width || camera->height != in->height || !tcfg_valid(t, k.g.iterations))
@@ -295,11 +309,15 @@ extern "C" lumo_status lumo_denoise_temporal(void* ctx, const lumo_denoise_in* i
     HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * DT_CNT_N, k.sm));
     clk.mark();
     k.prepare();
+    if (motion_w) k_dn_motion<<<k.pix_blocks, 256, 0, k.sm>>>(k.buf(DN_IN_MOT), k.buf(DN_IN_DEP), k.buf(DN_MOT), n);
     if ((st = k.firefly())) return st;
     clk.mark();
     const unsigned tiles = (unsigned)((k.W + DT_BX - 1) / DT_BX) * (unsigned)((k.H + DT_BY - 1) / DT_BY);
-    k_dn_reproject<<<tiles, DT_THREADS, 0, k.sm>>>(k.P, prev, next, cam_of(*camera),
-                                                   cam_of(has_prev ? c->dn_hist_cam : *camera), tc, cnt, k.W, k.H);
+    const DtCam cur = cam_of(*camera), prv = cam_of(has_prev ? c->dn_hist_cam : *camera);
+    if (motion_w)
+        k_dn_reproject<true><<<tiles, DT_THREADS, 0, k.sm>>>(k.P, prev, next, cur, prv, tc, cnt, k.W, k.H, k.buf(DN_MOT));
+    else
+        k_dn_reproject<false><<<tiles, DT_THREADS, 0, k.sm>>>(k.P, prev, next, cur, prv, tc, cnt, k.W, k.H, nullptr);
     clk.mark();
     k.variance();
     clk.mark();

@@ -5,6 +5,8 @@
 //                   the bilinear (else 3 x 3) gather of the previous call's history, the blend
 //   k_dn_tvar       step 6, one thread per pixel: the temporal variance where the history is long
 //   k_dn_history    one thread per pixel: the feedback iteration's colour into the history
+//   k_dn_motion     lumo_denoise_temporal_motion only: the per-pixel motion m that k_dn_reproject<true>
+//                   adds to the world position before it projects it (DESIGN.md §4g "Motion")
 //
 // The history is double-buffered (DtHist prev / next): k_dn_reproject reads `prev` at positions that
 // follow from the camera's motion while it and k_dn_history write `next`, so no kernel reads a plane
@@ -54,14 +56,26 @@ struct DtCfg {
     int max_history, min_history, stage_lds, has_prev;
 };
 
+// Step 1's addition of lumo_denoise_temporal_motion, one thread per pixel: m = motion_w[0..2] /
+// depth_w[1] (0 where no sample hit) into three planes of n doubles.
+__global__ __launch_bounds__(256) void k_dn_motion(const double* motion_w, const double* depth_w, double* m, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int k = 0; k < 3; ++k) m[(size_t)k * n + i] = dn_ratio(motion_w[4 * i + k], depth_w[4 * i + 1]);
+}
+
 // Steps 2 and 3 and step 4's u, v: false when the pixel has no history whatever the taps hold.
-__device__ __forceinline__ bool dt_project(const DtCam& cur, const DtCam& prv, int x, int y, double z, int W, int H,
+// MOTION: the point is carried back by the pixel's motion m first (P' = P + m); without it m is unused
+// and nothing is added.
+template <bool MOTION>
+__device__ __forceinline__ bool dt_project(const DtCam& cur, const DtCam& prv, int x, int y, double z, V3 m, int W, int H,
                                            double& u, double& v, double& zp) {
     const V3 screen = xf_pt_inv(cur.sctr, V3{(double)x + 0.5, (double)y + 0.5, 0.0});
     const V3 cpt = xf_pt_inv(cur.cts, screen);
     const V3 o = xf_pt_inv(cur.wtc, V3{0.0, 0.0, 0.0});
     const V3 d = normalize(xf_dir_inv(cur.wtc, normalize(cpt)));
-    const V3 P = o + z * d;
+    V3 P = o + z * d;
+    if constexpr (MOTION) P = P + m;
     const V3 cp = xf_pt(prv.wtc, P);
     if (!(cp.z > 0.0)) return false;
     const V3 q = xf_pt(prv.sctr, xf_pt(prv.cts, cp));
@@ -131,8 +145,11 @@ __device__ __forceinline__ bool dt_gather(const Src& S, const DtCfg& cfg, const 
 
 // Steps 2-5.  Reads P's guides, l and e[0] (k_dn_prepare's) and the history `prev`; writes e_acc to
 // P.e[0], its luminance to P.l (step 6's input), and m1, m2, N, n, z, hit to `next`.  cnt: DT_CNT_*.
+// MOTION: mot holds k_dn_motion's three planes; else it is not read.
+template <bool MOTION>
 __global__ __launch_bounds__(DT_THREADS) void k_dn_reproject(DnPlanes P, DtHist prev, DtHist next, DtCam cur, DtCam prv,
-                                                             DtCfg cfg, unsigned long long* cnt, int W, int H) {
+                                                             DtCfg cfg, unsigned long long* cnt, int W, int H,
+                                                             const double* mot) {
     __shared__ double tile[DT_NV * DT_CAP];
     __shared__ uint32_t tile_len[DT_CAP], tile_hit[DT_CAP];
     __shared__ int wave_box[DT_THREADS / 64][4];
@@ -146,7 +163,12 @@ __global__ __launch_bounds__(DT_THREADS) void k_dn_reproject(DnPlanes P, DtHist 
     bool cand = false;  // the pixel's taps decide whether it has history
     if (inside) {
         p = DnGuide{{P.n[0][i], P.n[1][i], P.n[2][i]}, P.z[i], P.hit[i]};
-        cand = cfg.has_prev && p.hit && dt_project(cur, prv, x, y, p.z, W, H, u, v, zp);
+        V3 m{0.0, 0.0, 0.0};
+        if constexpr (MOTION) {
+            const size_t n = (size_t)W * H;
+            m = V3{mot[i], mot[n + i], mot[2 * n + i]};
+        }
+        cand = cfg.has_prev && p.hit && dt_project<MOTION>(cur, prv, x, y, p.z, m, W, H, u, v, zp);
     }
     // the box of the block's taps: x0 - 1 .. x0 + 2 covers the 2 x 2 and the 3 x 3 around x0 or x0 + 1
     int box[4] = {INT_MAX, INT_MAX, INT_MIN, INT_MIN};  // min x, min y, max x, max y

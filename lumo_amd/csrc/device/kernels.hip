@@ -703,6 +703,7 @@ __global__ __launch_bounds__(64) void k_ring(DScene sc, Paths S, Tasks T, int n_
 
 // ------------------------------------------------------------------ feature buffers (lumo_render_features)
 #include "features.h"
+#include "motion.h"
 
 // ------------------------------------------------------------------ BDPT splats -> film taps
 // FilmTile::add_sample with splat = true (film/tile.rs:65-111): tone map, XYZ, white balance,
@@ -815,6 +816,7 @@ enum WorkId {
     W_BD_WDEPTH, W_BD_CAMO, W_BD_CAMD, W_BD_RNG0, W_BD_LAM0, W_BD_NB, W_BD_OFFB,
     W_CHECKS, W_BD_LM, W_BD_LMF, W_BD_CM, W_BD_CMF,
     W_FT_ALB, W_FT_NRM, W_FT_DEP, W_FT_FILM_A, W_FT_FILM_N, W_FT_FILM_D, W_FT_DUMP_I, W_FT_DUMP_D,
+    W_MO_DLT, W_MO_FILM, W_MO_DUMP,
     W_SET0,  // pass set k's field f: W_SET0 + k * F_SET_COUNT + f
     W_COUNT = W_SET0 + 4 * F_SET_COUNT
 };
@@ -2368,12 +2370,16 @@ lumo_status render_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lum
 // no ray sort), k_features and the pass's share of the three planes.  It plans no schedule and
 // leaves the record of lumo_last_schedule alone.  The camera rays count as closest queries with the
 // traversal counters of class 0.
+// With motion or mdump (motion.h) every pass also launches k_motion and the motion film over the same
+// hits; the features themselves are then made only when out is given.
 constexpr int FT_DUMP_DOUBLES = 28;  // t 1, p 3, ng 3, ns 3, n 3, uv 2, albedo 4, albedo_rgb 3, raster 2, lambda 4
 lumo_status render_features_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_tasks, lumo_feature_planes* out,
-                                 const lumo_feature_dump* dump) {
+                                 const lumo_feature_dump* dump, const lumo_motion_planes* motion = nullptr,
+                                 const lumo_motion_dump* mdump = nullptr) {
     if (!c.has_scene) return LUMO_ERR_NO_SCENE;
     if (!c.has_camera) return LUMO_ERR_NO_CAMERA;
     if (n_tasks == 0) return LUMO_OK;
+    const bool with_motion = motion || mdump, with_features = !with_motion || out;
     Render R{tasks, n_tasks, nullptr, nullptr, 0};
     R.features = true;
     lumo_status st = build_slots(R);
@@ -2402,6 +2408,19 @@ lumo_status render_features_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_t
                        dd + 22 * m, dd + 24 * m};
         F.dump_p = N;
     }
+    Motion M{};
+    double* md = nullptr;
+    if (with_motion) {
+        M.vprev = c.vprev ? c.vprev : c.sc.vertices;
+        M.dlt = wbuf<double>(c, W_MO_DLT, 3 * (size_t)N, st);
+        M.film_m = wbuf<double>(c, W_MO_FILM, 4 * (size_t)N, st);
+        if (mdump) {
+            const size_t mm = (size_t)tasks[0].samples * (size_t)N;  // a dump: one task
+            md = wbuf<double>(c, W_MO_DUMP, 6 * mm, st);
+            M.d = MotionDump{md, md + 3 * mm};
+            M.dump_p = N;
+        }
+    }
     if (st) return st;
     if ((st = setup_render(c, R))) return st;
     hipStream_t sm = c.streams[0];
@@ -2410,6 +2429,7 @@ lumo_status render_features_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_t
         z.add(F.film_a, sizeof(double) * 4 * N);
         z.add(F.film_n, sizeof(double) * 4 * N);
         z.add(F.film_d, sizeof(double) * 4 * N);
+        if (with_motion) z.add(M.film_m, sizeof(double) * 4 * N);
         k_zero_list<<<std::min(ceil_div((uint64_t)4 * N, BLOCK), 2048), BLOCK, 0, sm>>>(z);
     }
     const int gN = ceil_div(N, BLOCK);
@@ -2426,28 +2446,44 @@ lumo_status render_features_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_t
                 [&](auto K, const TravLaunch& l) { launch_closest_q<decltype(K)::value>(l, c.sc, S, S.qs[0], 0u); }, sm,
                 true);
         }
-        {
+        if (with_features) {
             StageTimer tm(c, c.o.timing, ST_SHADE, sm);
             by_fx(c.sc.full, [&](auto FX) {
                 k_features<decltype(FX)::value><<<gN, BLOCK, 0, sm>>>(c.sc, S, F, c.cam, S.qs[0], (uint32_t)pass);
             });
         }
-        {
+        if (with_features) {
             StageTimer tm(c, c.o.timing, ST_FILM, sm);
             if (R.max_P <= BLOCK)
                 k_feature_film<<<n_t, BLOCK, 0, sm>>>(S, F, R.T, c.cam, 0);
             else
                 k_feature_gather<<<gN, BLOCK, 0, sm>>>(S, F, R.T, c.cam, N);
         }
+        if (with_motion) {
+            {
+                StageTimer tm(c, c.o.timing, ST_SHADE, sm);
+                by_fx(c.sc.full, [&](auto FX) {
+                    k_motion<decltype(FX)::value><<<gN, BLOCK, 0, sm>>>(c.sc, S, M, S.qs[0], (uint32_t)pass);
+                });
+            }
+            StageTimer tm(c, c.o.timing, ST_FILM, sm);
+            if (R.max_P <= BLOCK)
+                k_motion_film<<<n_t, BLOCK, 0, sm>>>(S, M, R.T, c.cam, 0);
+            else
+                k_motion_gather<<<gN, BLOCK, 0, sm>>>(S, M, R.T, c.cam, N);
+        }
         k_zero_counts<<<1, 64, 0, sm>>>(S.counts, nullptr);
         HIPCHK(hipGetLastError());
         if (c.o.timing) resolve_timers(c);
     }
     // the planes: straight into the caller's buffers when they lie back to back in slot order
-    const double* films[3] = {F.film_a, F.film_n, F.film_d};
+    const double* films[4] = {F.film_a, F.film_n, F.film_d, M.film_m};
     std::vector<double> host;
-    for (int k = 0; k < 3 && out; ++k) {
-        auto plane = [&](size_t i) { return k == 0 ? out[i].albedo_w : (k == 1 ? out[i].normal_w : out[i].depth_w); };
+    for (int k = 0; k < 4; ++k) {
+        if (k < 3 ? !out : !motion) continue;
+        auto plane = [&](size_t i) {
+            return k == 0 ? out[i].albedo_w : (k == 1 ? out[i].normal_w : (k == 2 ? out[i].depth_w : motion[i].motion_w));
+        };
         bool any = false, direct = plane(0) != nullptr;
         for (size_t i = 0; i < n_tasks; ++i) {
             any = any || plane(i) != nullptr;
@@ -2478,6 +2514,11 @@ lumo_status render_features_impl(Ctx& c, const lumo_tile_task* tasks, size_t n_t
             if (hd[k]) HIPCHK(hipMemcpyAsync(hd[k], dd + o * m, sizeof(double) * per[k] * m, hipMemcpyDeviceToHost, sm));
             o += (size_t)per[k];
         }
+    }
+    if (mdump) {
+        const size_t mm = (size_t)tasks[0].samples * (size_t)N;
+        if (mdump->bary) HIPCHK(hipMemcpyAsync(mdump->bary, md, sizeof(double) * 3 * mm, hipMemcpyDeviceToHost, sm));
+        if (mdump->delta) HIPCHK(hipMemcpyAsync(mdump->delta, md + 3 * mm, sizeof(double) * 3 * mm, hipMemcpyDeviceToHost, sm));
     }
     unsigned long long tc[TC_ALL];
     HIPCHK(hipMemcpyAsync(tc, S.tcount, sizeof(tc), hipMemcpyDeviceToHost, sm));
@@ -2692,11 +2733,12 @@ lumo_status lumo_debug_paths(void* ctx, const lumo_tile_task* task, lumo_path_du
     return st;
 }
 
-// Feature planes of n tasks (features.h); the sampler applies to this call only.
-lumo_status lumo_render_features(void* ctx, const lumo_tile_task* tasks, size_t n, const lumo_feature_cfg* cfg,
-                                 lumo_feature_planes* out) {
+// Feature planes of n tasks (features.h), with `motion` also their motion planes (motion.h; out may then
+// be NULL); the sampler applies to this call only.
+static lumo_status render_features_call(void* ctx, const lumo_tile_task* tasks, size_t n, const lumo_feature_cfg* cfg,
+                                        lumo_feature_planes* out, const lumo_motion_planes* motion) {
     Ctx* c = static_cast<Ctx*>(ctx);
-    if (!c || (!tasks && n) || (!out && n)) return LUMO_ERR_INVALID;
+    if (!c || (!tasks && n) || (!out && !motion && n)) return LUMO_ERR_INVALID;
     const int sampler = cfg ? cfg->sampler : LUMO_SAMPLER_MULTI_JITTERED;
     if (sampler < LUMO_SAMPLER_MULTI_JITTERED || sampler > LUMO_SAMPLER_SOBOL) return LUMO_ERR_INVALID;
     for (size_t i = 0; i < n && sampler == LUMO_SAMPLER_SOBOL; ++i)
@@ -2708,9 +2750,32 @@ lumo_status lumo_render_features(void* ctx, const lumo_tile_task* tasks, size_t 
     if (n == 0) st = render_features_impl(*c, tasks, 0, out, nullptr);  // the scene and camera checks
     for (size_t i = 0; i < n && !st;) {
         const size_t j = chunk_end(tasks, n, i, max_paths);
-        st = render_features_impl(*c, tasks + i, j - i, out + i, nullptr);
+        st = render_features_impl(*c, tasks + i, j - i, out ? out + i : nullptr, nullptr, motion ? motion + i : nullptr);
         i = j;
     }
+    c->sampler = LUMO_SAMPLER_MULTI_JITTERED;
+    return st;
+}
+
+lumo_status lumo_render_features(void* ctx, const lumo_tile_task* tasks, size_t n, const lumo_feature_cfg* cfg,
+                                 lumo_feature_planes* out) {
+    return render_features_call(ctx, tasks, n, cfg, out, nullptr);
+}
+
+lumo_status lumo_render_features_motion(void* ctx, const lumo_tile_task* tasks, size_t n, const lumo_feature_cfg* cfg,
+                                        lumo_feature_planes* out, const lumo_motion_planes* motion) {
+    if (!motion) return LUMO_ERR_INVALID;
+    return render_features_call(ctx, tasks, n, cfg, out, motion);
+}
+
+// Test hook: the per-sample motion records of one task, with lumo_debug_set_sampler's sampler.
+lumo_status lumo_debug_motion(void* ctx, const lumo_tile_task* task, lumo_motion_dump* dump) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c || !task || !dump) return LUMO_ERR_INVALID;
+    if (c->debug_sampler == LUMO_SAMPLER_SOBOL && task->total_samples > 1023) return LUMO_ERR_INVALID;
+    HIPCHK(hipSetDevice(c->device));
+    c->sampler = c->debug_sampler;
+    const lumo_status st = render_features_impl(*c, task, 1, nullptr, nullptr, nullptr, dump);
     c->sampler = LUMO_SAMPLER_MULTI_JITTERED;
     return st;
 }

@@ -533,6 +533,21 @@ lumo_status lumo_scene_update_vertices(void* ctx, int32_t first, int32_t count, 
     return LUMO_OK;
 }
 
+// The present vertices become the previous ones of the motion feature (device/motion.h).
+lumo_status lumo_scene_motion_mark(void* ctx) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    if (!c) return LUMO_ERR_INVALID;
+    if (!c->has_scene) return LUMO_ERR_NO_SCENE;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = 3 * (size_t)c->n_vertices;
+    if (!c->vprev) WB_TRY(rf_get(*c, &c->vprev, n));
+    hipStream_t sm = c->streams[0];
+    if (n > 0) k_rf_mark<<<std::min(blocks((n + 1) / 2), WB_STAT_GRID), WB_BLOCK, 0, sm>>>(c->vprev, c->sc.vertices, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(sm));
+    return LUMO_OK;
+}
+
 lumo_status lumo_scene_refit_info(void* ctx, lumo_refit_info* info) {
     Ctx* c = static_cast<Ctx*>(ctx);
     if (!c || !info) return LUMO_ERR_INVALID;

@@ -9,6 +9,7 @@
 //   k_rf_fit             the boxes bottom-up, a quad of lanes per node; BLASes, then the world trees
 //   k_rf_rootarea        per root node the area k_wb_rootarea gives its tree
 //   k_rf_copy            the refreshed arrays into the staged sets (hot / TOP), 16 B per lane
+//   k_rf_mark            lumo_scene_motion_mark: the vertices into the previous vertices, 16 B per lane
 // The roundings (wb_f_down / wb_f_up) and the reductions (k_wb_stats_*) are the builder's own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -296,6 +297,16 @@ __global__ __launch_bounds__(WB_BLOCK) void k_rf_rootarea(RfWork w) {
 
 __global__ __launch_bounds__(WB_BLOCK) void k_rf_copy(uint4* dst, const uint4* src, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * WB_BLOCK + threadIdx.x; i < n16; i += (size_t)gridDim.x * WB_BLOCK) dst[i] = src[i];
+}
+
+// lumo_scene_motion_mark: the vertex array into the previous vertices, 16 B per lane; n doubles, of
+// which an odd last one goes alone (3 per vertex: the byte count is a multiple of 8 only)
+__global__ __launch_bounds__(WB_BLOCK) void k_rf_mark(double* dst, const double* src, size_t n) {
+    const size_t n16 = n / 2, first = (size_t)blockIdx.x * WB_BLOCK + threadIdx.x;
+    const double2* s2 = reinterpret_cast<const double2*>(src);
+    double2* d2 = reinterpret_cast<double2*>(dst);
+    for (size_t i = first; i < n16; i += (size_t)gridDim.x * WB_BLOCK) d2[i] = s2[i];
+    if (first == 0 && (n & 1)) dst[n - 1] = src[n - 1];
 }
 
 }  // namespace dev
